@@ -12,6 +12,11 @@ A step = one full hooked forward over one batch resident in HBM: ViT-H/14 on B*3
 32 decoder + 8 gated cross-attention layers with the ICV hook on every decoder layer, LM head (logits for all
 positions).  Forward-only data parallel: questions shard across ranks, no data-path collective ("weak").
 Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds what takes runs of its own: the CPU
+baseline, the unfused PyTorch-ROCm run of the oracle (gpu_unfused_baseline) and, in the sliced configuration, the two
+timed regions the GEMM roofline is measured in.  --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (float32; integer outputs as float64), from inputs that are seeded, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -214,13 +219,17 @@ def frontend_bench(args, eng, arch, batch, hooks, B, n_img, dev):
     t_fed = timed(fed, args.steps)
     # (4) the feeder at full tilt beside the forward: `k` extra batches per step on the side stream
     k = 8
+    last = [None]
     def beside(iters):                                    # (submit only: a get() would make the main stream a consumer of every batch)
         for i in range(iters):
-            eng.forward(**batch, **hooks)
+            last[0] = eng.forward(**batch, **hooks)
             for j in range(k):
                 feeder.submit(host[j & 1])
     beside(2)
     t_beside = timed(beside, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(last[0], batch, None))
+    last[0] = None
     res = {
         "metric": "frontend images/s: uint8 host -> pinned staging -> H2D -> normalised bf16 on the device (licv.image_feeder), headline forward running concurrently",
         "value": args.steps * k * n / t_beside, "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -345,12 +354,57 @@ def build_trainer(arch, sd, dev, B, S, n_img, min_len, rank, hw=None):
     return trainer, (to(stu), to(tea), (sl - ans).to(dev), (tl - ans).to(dev))
 
 
+DUMP_LOGIT_ROWS = 256          # 256 rows of a 32 k vocabulary: 33 MB in float32 (the whole [8, 800, V] logits would be 820 MB)
+
+
+def step_outputs(out, batch, trainer) -> dict:
+    """What a caller of the timed path receives from its last step, as named tensors.
+    Training: the ICV parameters the step left, their accumulated gradients (between optimiser steps) and the optimiser
+    step's log.  Generate: the token rows.  Forward: the logits [B, S, V] at each question's last real token and at a
+    fixed, seeded sample of DUMP_LOGIT_ROWS real-token positions (`logits_sample_rows` = their flat b * S + s indices)."""
+    if trainer is not None:
+        enc = trainer.m.icv_encoder
+        res = {"icv": enc.icv, "alpha": enc.alpha}
+        for name, g in (("icv_grad", enc.icv.grad), ("alpha_grad", enc.alpha.grad)):
+            if g is not None:
+                res[name] = g
+        for k, v in (out or {}).items():
+            res[k] = torch.tensor(float(v), dtype=torch.float64)
+        return res
+    if out.dim() == 2:
+        return {"sequences": out}
+    B, S, V = out.shape
+    am = batch["attention_mask"]
+    real = am.reshape(-1).nonzero().squeeze(1).cpu()
+    g = torch.Generator().manual_seed(426)
+    rows = real[torch.randperm(real.numel(), generator=g)[:DUMP_LOGIT_ROWS]].sort().values
+    last = am.sum(1) - 1
+    return {"logits_last": out[torch.arange(B, device=out.device), last],
+            "logits_sample": out.reshape(B * S, V).index_select(0, rows.to(out.device)),
+            "logits_sample_rows": rows}
+
+
+def dump_outputs(out_dir, arrays: dict) -> None:
+    """arrays -> out_dir/<name>.npy: float64 stays, other floating point as float32, integers as float64 (exact)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.to(torch.float32) if t.is_floating_point() else t.to(torch.float64)
+        np.save(out_dir / f"{name}.npy", t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="idefics9b_32shot_bs8", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: cpu_baseline, gpu_unfused_baseline "
+                    "and the roofline regions of the sliced configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--prefetch-mib", type=int, default=-1, help="decode steps: MiB of the next projection's weights a side stream reads ahead (licv_runner_option 2); -1 = the library's default")
     ap.add_argument("--no-gpu-baseline", action="store_true", help="skip the unfused PyTorch-ROCm run of the oracle on the GPU (row G0)")
@@ -363,6 +417,8 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL; default).  'gloo' only to rehearse the multi-rank code path "
                     "on a box with fewer GPUs than ranks (ranks then share devices: timings are meaningless)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: start N ranks as fresh child processes (one per GPU, RCCL) BEFORE this process has
@@ -441,8 +497,8 @@ def main():
         eng.batch_streams = args.batch_streams
     if os.environ.get("LICV_NO_FOLD") and hasattr(eng, "fold_residual"):
         eng.fold_residual = False
-    want_g0 = (rank == 0 and world == 1 and not is2 and not training and "generate" not in args.workload and not args.no_gpu_baseline
-               and not args.no_hooks)
+    want_g0 = (args.full and rank == 0 and world == 1 and not is2 and not training and "generate" not in args.workload
+               and not args.no_gpu_baseline and not args.no_hooks)
     if not want_g0:
         del sd
     torch.cuda.empty_cache()
@@ -513,6 +569,8 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     ops.set_profiler(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(out, batch, trainer))
     del out
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
@@ -529,9 +587,10 @@ def main():
     # roofline of the dominant kernel therefore comes from a further timed region of the same step with the slices off (kernels of
     # one stream never overlap): per-launch HIP event pairs over min(steps, 6) steps, its ms per step reported beside it; a short
     # region with event pairs in the sliced configuration gives the figures kept under "overlapped" (union of the launch intervals,
-    # mean start-to-end time).
+    # mean start-to-end time).  Both regions run with --full only.
     overlapped = None
-    if sliced:
+    roof_regions = sliced and args.full
+    if roof_regions:
         n_sl = int(eng.batch_streams)
         o_steps = min(args.steps, 3)                          # short region with event pairs ON in the sliced configuration
         ops.set_profiler([])                                  # (two untimed steps first: the Python-level path allocates its own buffers)
@@ -578,8 +637,8 @@ def main():
         eng.batch_streams = n_sl
         ser = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(serial_steps))
         overlapped["serial_pass"] = {"steps": serial_steps, "ms_per_step_median": ser[len(ser) // 2]}
-    roof_steps = overlapped["serial_pass"]["steps"] if sliced else args.steps
-    roof_elapsed = 1e-3 * sum(marks[i].elapsed_time(marks[i + 1]) for i in range(roof_steps)) if sliced else elapsed
+    roof_steps = overlapped["serial_pass"]["steps"] if roof_regions else args.steps
+    roof_elapsed = 1e-3 * sum(marks[i].elapsed_time(marks[i + 1]) for i in range(roof_steps)) if roof_regions else elapsed
 
     # roofline of the dominant kernel (the bf16 MFMA GEMM) from the in-run event pairs
     def agg(kind):
@@ -631,11 +690,17 @@ def main():
                      "avg_launch_us": 1e6 * tg / ng if ng else None, "gemm_share_of_step": tg / roof_elapsed if roof_elapsed else None,
                      **({"measured_in": f"second timed region of {roof_steps} steps with the batch slices off (one stream, kernels do not overlap): "
                                         f"{overlapped['serial_pass']['ms_per_step_median']:.1f} ms per step there; 'value' is the sliced configuration",
-                         "overlapped": overlapped} if sliced else {})},
+                         "overlapped": overlapped} if roof_regions else {})},
         "whole_path": {"tflop_per_question": fq["total"] / 1e12, "achieved_tflops_per_gpu": fq["total"] * B * args.steps / elapsed / 1e12,
                        "frac_of_mfma_peak": fq["total"] * B * args.steps / elapsed / 1e12 / PEAK_BF16_TFLOPS},
     }
     res.update(dist_info)
+    if sliced and not roof_regions:
+        # the timed steps ran without event pairs: the per-launch figures (and Idefics2's FLOPs as launched) need the regions above
+        res["roofline"] = {k: res["roofline"][k] for k in ("bound", "kernel", "peak", "unit", "peak_note")}
+        res["roofline"].update(achieved=None, frac=None, measured_in="not measured: run with --full")
+        if is2:
+            res["whole_path"] = None
     if generating or "student" in args.workload:
         # weight-streaming shapes (what the reference really hooks): every weight matrix is read once per pass and used
         # on 24-256 rows, so the bound of the STEP is the HBM stream of the weights; achieved = those bytes / the step's time
@@ -687,7 +752,7 @@ def main():
         res["vs_baseline_note"] = ("null: BASELINE.md holds no published number for this metric; the measured 'reference on GPU' denominator "
                                    "(row G0) is gpu_unfused_baseline, native/unfused = %.2fx" % g0["native_over_unfused"])
         del sd
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = (cpu_baseline_idefics2(arch, S, n_img, IDEFICS2_IMAGE[preset]) if is2 else
                                cpu_baseline_generate(arch, S, n_img) if generating else cpu_baseline(arch, S, n_img))
     if rank == 0:

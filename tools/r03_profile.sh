@@ -9,7 +9,7 @@ OUT=gpurun_out/r03
 mkdir -p $OUT
 if [ "$QUICK" = "partB" ]; then
 for W in idefics9b_train_bs8 idefics9b_generate_bs8 idefics9b_student_bs8 idefics2_8b_1shot_bs8 idefics2_8b_32shot_bs8 idefics2_8b_32shot_fp8_bs8 frontend_images_bs8; do
-  timeout -k 10 400 python3 bench.py --workload $W --steps 8 --warmup 3 > $OUT/bench_$W.json.log 2>$OUT/bench_$W.err
+  timeout -k 10 400 python3 bench.py --workload $W --steps 8 --warmup 3 --full > $OUT/bench_$W.json.log 2>$OUT/bench_$W.err
   echo "$W rc=$?"
 done
 ls $OUT; exit 0; fi
@@ -17,7 +17,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k
 python3 tools/summarize_rocprof.py $OUT/kt $OUT/bench_headline_serial_kernel_stats.md "bench.py --steps 5 --warmup 2 --batch-streams 1 (7 forwards, one stream: the configuration roofline.achieved is measured in) on 1xMI355X, headline workload, build at $COMMIT" > /dev/null
 echo "serial kernel trace done"
 if [ "$QUICK" = "quick" ]; then cp $OUT/kt/*/*kernel_stats.csv $OUT/kernel_stats_full.csv 2>/dev/null; rm -rf $OUT/kt; ls $OUT; exit 0; fi
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_headline.json.log 2>$OUT/bench_headline.err || exit 1
+timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_headline.json.log 2>$OUT/bench_headline.err || exit 1
 echo "headline done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt2 -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-gpu-baseline --no-profiler > $OUT/kt2.log 2>&1 || exit 1
 python3 tools/summarize_rocprof.py $OUT/kt2 $OUT/bench_headline_sliced_kernel_stats.md "bench.py --steps 5 --warmup 2 --no-profiler (7 forwards, product configuration: two batch slices on two HIP streams, native layer runner; a kernel's duration includes the time the other slice's kernels held CUs) on 1xMI355X, build at $COMMIT" > /dev/null
@@ -33,7 +33,7 @@ p="$OUT/pmc_headline_gemm.json"; d=json.load(open(p)); d["commit"]="$COMMIT"; js
 PY
 if [ "$QUICK" = "partA" ]; then rm -rf $OUT/kt $OUT/kt2 $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE; ls $OUT; exit 0; fi
 for W in idefics9b_train_bs8 idefics9b_generate_bs8 idefics9b_student_bs8 idefics2_8b_1shot_bs8 idefics2_8b_32shot_bs8 idefics2_8b_32shot_fp8_bs8 frontend_images_bs8; do
-  timeout -k 10 400 python3 bench.py --workload $W --steps 8 --warmup 3 > $OUT/bench_$W.json.log 2>$OUT/bench_$W.err
+  timeout -k 10 400 python3 bench.py --workload $W --steps 8 --warmup 3 --full > $OUT/bench_$W.json.log 2>$OUT/bench_$W.err
   echo "$W rc=$?"
 done
 rm -rf $OUT/kt $OUT/kt2 $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE
