@@ -22,8 +22,9 @@ extern "C" {
 
 /* Bumped whenever an entry point is added, removed or changes its arguments; licv/_lib.py holds the same constant and refuses a
  * library that answers anything else.  1 = round 1; 2 = rounds 2-3 (fp8, split-K slices, runner, front-end, backward, image input);
- * 3 = round 4 (lab library split off; weight-streaming GEMM; beam scoring; decode-step fusion). */
-#define LICV_ABI_VERSION 6
+ * 3-6 = round 4 (lab library split off; weight-streaming GEMM; beam scoring; decode-step fusion; backward options; RMSNorm backward
+ * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step). */
+#define LICV_ABI_VERSION 7
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
 enum { LICV_OK = 0, LICV_E_BADARG = -1, LICV_E_UNSUPPORTED = -2, LICV_E_HIP = -3 };
@@ -401,6 +402,47 @@ typedef struct {
 } licv_beam_step_args;
 int64_t licv_beam_step_scratch_bytes(int64_t B, int64_t nb);
 int licv_beam_step(const licv_beam_step_args* a, void* stream);
+
+/* ---- sampled decoding (do_sample=True) of hooked generate: transformers 5.x _sample (generation/utils.py:2794-2930) and the
+ * do_sample branch of _beam_search (_get_top_k_continuations, :3090-3125, :3388-3420) with the warpers of _get_logits_processor
+ * (:1123-1330) in hf order: min-new-tokens EOS suppression, temperature, top-k, top-p, min-p (generation/logits_process.py).
+ * Randomness: Philox4x32-10 keyed by the 64-bit seed, counter (step = cur - P, question, beam, token); u = ((x >> 8) + 0.5) * 2^-24.
+ * Ties: top-k keeps every score >= the k-th largest; top-p removes in ascending score order, the higher token id first among equal
+ * scores, while the removed mass stays <= (1 - top_p) * total (mass = exp(score - max) in 2^-40 fixed point); min-p keeps
+ * exp(score - max) >= min_p; min_tokens_to_keep = 1 without beams, 2 with. ---- */
+typedef struct {
+    float temperature;                                 /* > 0 (hf TemperatureLogitsWarper: scores / T in fp32) */
+    int64_t top_k;                                     /* 0 = off; raised to min_tokens_to_keep (hf TopKLogitsWarper) */
+    float top_p;                                       /* (0, 1]; 1 = off (hf TopPLogitsWarper) */
+    float min_p;                                       /* [0, 1]; 0 = off (hf MinPLogitsWarper) */
+    uint64_t seed;                                     /* Philox key */
+} licv_sample_params;
+
+/* num_beams == 1 (hf _sample with do_sample): per row the warpers on the fp32 logits, then the inverse-CDF draw over the kept tokens
+ * in token-id order (the smallest id whose prefix mass exceeds u * total).  Finished rows take the pad id.  ONE launch per step. */
+typedef struct {
+    const void* logits; int logits_dtype;              /* (B, V) rows, bf16 or fp32, row stride ld (elements); V <= 65536 */
+    int64_t ld;
+    int64_t B, V;
+    int64_t* ids; int64_t ids_ld;                      /* the running (B, max_len) id buffer: column cur is written */
+    int64_t max_len, cur, P;                           /* cur = column being written, P = prompt length */
+    uint8_t* unfinished;                               /* (B) 1 while a row generates (hf unfinished_sequences), updated in place */
+    int64_t* next_tokens;                              /* (B) the tokens just written (the next step's input ids) */
+    int64_t eos, pad;                                  /* eos -1 = none */
+    int suppress_eos;                                  /* min_new_tokens not reached: EOS scores -inf */
+    int32_t* flags;                                    /* [0] = 1 while some row generates and cur + 1 < max_len (last workgroup) */
+    int32_t* sync;                                     /* 2 int32, zero before the first call; the kernel leaves them zero */
+} licv_sample_step_args;
+int licv_sample_step(const licv_sample_step_args* a, const licv_sample_params* p, void* stream);
+
+/* num_beams > 1 (beam-search multinomial sampling): the warpers act on log_softmax(logits) (beam.hip's order of evaluation) / T,
+ * filtered scores are -inf and the carried beam scores are these processed values (not renormalised).  2*nb continuations per
+ * question are drawn without replacement from softmax(score + running score) over (nb x V) as the 2*nb largest Gumbel keys
+ * score + running + (-log(-log u)) (ties: the lower flat index); the un-noised scores go on to licv_beam_step's bookkeeping, which is
+ * unchanged, KV row table included.  Fewer than 2*nb candidates of non-zero probability in a question: flags[0] bit 1 (value 2) is
+ * set (torch.multinomial raises there).  a->scratch: >= licv_beam_sample_scratch_bytes(B, nb), zero before the first call. */
+int64_t licv_beam_sample_scratch_bytes(int64_t B, int64_t nb);
+int licv_beam_sample_step(const licv_beam_step_args* a, const licv_sample_params* p, void* stream);
 
 /* ---- device-side front-end: integer rules between the collator / processor and the first GEMM ---- */
 /* Idefics image_attention_mask (B, S, n_images) int32 one-hot rows from input_ids (B, S) int64 by the incremental rule of

@@ -12,8 +12,7 @@
 // combines the per-question "keep going" flags.  Ties are broken towards the LOWER flat candidate index (beam * vocab + token)
 // everywhere - a stable descending sort.  (The first version did everything in ONE workgroup per question: 8 workgroups reading
 // 3 x 32002 logits three times took 278 us per step.)
-#include "common.h"
-#include <limits.h>
+#include "sample_common.h"
 
 #define BEAM_THREADS 256
 #define BEAM_MAX_NB 8
@@ -38,11 +37,23 @@ __device__ __forceinline__ float beam_block_reduce(float v, bool is_max, float* 
 // then cand_x[((b*nb + k)*CHUNKS + c)*KEEP + j], then cand_i (token ids, int32) at the same index
 __host__ __device__ inline int64_t beam_scratch_floats(int64_t B, int64_t nb) { return B * nb * BEAM_CHUNKS * (2 + 2 * 2 * nb); }
 
-template <int KEEP>
+// beam-search multinomial sampling (licv_beam_sample_step): the SAMPLE instantiations of the two kernels read each beam's log-softmax
+// statistics and kept set from the pre-pass (beam_sample_prep_k) and carry the un-noised score of every candidate beside its Gumbel key
+struct BeamSampleCtx {
+    const float* bst;                     // (B*nb, 4): max, log(sum of exp(x - max)), max processed score, unused
+    const uint32_t* thr;                  // (B*nb, 2): kept set (t, c) of sample_common.h
+    float* cand_a;                        // beside cand_x (which then holds the keys): the un-noised scores
+    int* err;                             // questions with fewer than 2*nb candidates of non-zero probability (left zero)
+    uint64_t seed; float temperature;
+};
+
+template <int KEEP, bool SAMPLE = false>
 __global__ __launch_bounds__(BEAM_THREADS)
-void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __restrict__ cand_x, int* __restrict__ cand_i) {
+void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __restrict__ cand_x, int* __restrict__ cand_i,
+                 BeamSampleCtx sc = BeamSampleCtx()) {
     constexpr int NB = KEEP / 2;
     __shared__ float sx[BEAM_CHUNK_MAX];
+    __shared__ float sa[SAMPLE ? BEAM_CHUNK_MAX : 1];
     __shared__ float red[BEAM_THREADS / 64];
     __shared__ float s_wv[BEAM_THREADS / 64]; __shared__ int s_wi[BEAM_THREADS / 64];
     const int b = blockIdx.x / BEAM_CHUNKS, c = blockIdx.x % BEAM_CHUNKS, tid = threadIdx.x;
@@ -52,6 +63,26 @@ void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __rest
     const int i0 = c * ch, n = max(0, min(ch, (int)V - i0));
     for (int beam = 0; beam < NB; ++beam) {
         const int64_t row = (int64_t)b * a.q_stride_rows + (int64_t)beam * a.beam_stride_rows;
+        const int64_t slot = ((int64_t)b * NB + beam) * BEAM_CHUNKS + c;
+        if constexpr (SAMPLE) {
+            // score = (log_softmax(x) with EOS suppressed) / T, -inf outside the kept set; key = score + running score + Gumbel noise
+            const int64_t bk = (int64_t)b * NB + beam;
+            const float bmx = sc.bst[bk * 4], blse = sc.bst[bk * 4 + 1], run = a.run_scores_in[bk];
+            const KeptSet S{sc.thr[bk * 2], (int)sc.thr[bk * 2 + 1]};
+            const uint32_t step = (uint32_t)(a.cur - a.P);
+            for (int i = tid; i < n; i += BEAM_THREADS) {
+                const int tok = i0 + i;
+                const float x = a.logits_dtype == LICV_F32 ? reinterpret_cast<const float*>(a.logits)[row * a.ld + tok]
+                                                           : bf2f(reinterpret_cast<const bf16_t*>(a.logits)[row * a.ld + tok]);
+                float y = ((x - bmx) - blse) / sc.temperature;
+                if (a.suppress_eos && tok == a.eos) y = -INFINITY;
+                const float acc = y + run;
+                const bool keep = kept_in(f2key(y), tok, S) && acc > -INFINITY;
+                sx[i] = keep ? acc + gumbel_noise(philox_x0(sc.seed, step, (uint32_t)b, (uint32_t)beam, (uint32_t)tok)) : __int_as_float(0x7fc00000);
+                sa[i] = acc;
+            }
+            __syncthreads();
+        } else {
         float mx = -INFINITY;
         for (int i = tid; i < n; i += BEAM_THREADS) {
             const float x = a.logits_dtype == LICV_F32 ? reinterpret_cast<const float*>(a.logits)[row * a.ld + i0 + i]
@@ -63,10 +94,10 @@ void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __rest
         float z = 0.f;
         for (int i = tid; i < n; i += BEAM_THREADS) z += expf(sx[i] - mx);
         z = beam_block_reduce(z, false, red);
-        const int64_t slot = ((int64_t)b * NB + beam) * BEAM_CHUNKS + c;
         if (tid == 0) { stats[slot * 2] = mx; stats[slot * 2 + 1] = z; }
         if (a.suppress_eos && a.eos >= i0 && a.eos < i0 + n && tid == 0) sx[a.eos - i0] = -INFINITY;   // ranked as -inf, still part of the sum
         __syncthreads();
+        }
         // KEEP rounds of a block arg-max over the chunk image (ties: the lower token id); a taken entry becomes NaN-free "-inf, skipped"
         for (int r = 0; r < KEEP; ++r) {
             float bv = -INFINITY; int bi = INT_MAX;
@@ -84,6 +115,7 @@ void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __rest
             if (tid == 0) {
                 cand_x[slot * KEEP + r] = gv;
                 cand_i[slot * KEEP + r] = gi == INT_MAX ? INT_MAX : i0 + gi;
+                if constexpr (SAMPLE) sc.cand_a[slot * KEEP + r] = gi == INT_MAX ? -INFINITY : sa[gi];
                 if (gi != INT_MAX) sx[gi] = __int_as_float(0x7fc00000);       // taken: NaN, skipped by `x == x`
             }
             __syncthreads();
@@ -92,15 +124,18 @@ void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __rest
 }
 
 
-template <int KEEP>
+template <int KEEP, bool SAMPLE = false>
 __global__ __launch_bounds__(BEAM_THREADS)
-void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const float* __restrict__ cand_x, const int* __restrict__ cand_i) {
+void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const float* __restrict__ cand_x, const int* __restrict__ cand_i,
+                   BeamSampleCtx sc = BeamSampleCtx()) {
     constexpr int NB = KEEP / 2;
     constexpr int NC = NB * BEAM_CHUNKS * KEEP;                   // surviving candidates of a question
     __shared__ float s_lse[BEAM_MAX_NB], s_mx[BEAM_MAX_NB];
     __shared__ float s_wv[BEAM_THREADS / 64]; __shared__ int s_wi[BEAM_THREADS / 64];
     __shared__ int s_wp[BEAM_THREADS / 64];
     __shared__ float lpv[NC]; __shared__ int lpi[NC];
+    __shared__ float lpa[SAMPLE ? NC : 1];                        // SAMPLE: lpv holds the Gumbel keys, lpa the un-noised scores
+    __shared__ float s_amax; __shared__ int s_err;
     __shared__ float top_lp[KEEP]; __shared__ int top_ix[KEEP];
     __shared__ int plan_run_src[NB], plan_run_tok[NB];            // new running row r <- running_in[src] with [cur] = tok
     __shared__ int plan_fin_src[NB], plan_fin_tok[NB];            // new finished row f <- finished_in[src] (tok < 0) or running_in[src] with [cur] = tok
@@ -108,7 +143,13 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
     const int lane = tid & 63, wave = tid >> 6;
     const int64_t V = a.V;
     // ---- (1) per-beam log-softmax statistics from the chunk partials: max over chunks, sum of exp rescaled to it
-    if (tid < NB) {
+    if constexpr (SAMPLE) {
+        if (tid == 0) {                                           // the question's largest score + running score (kept in every beam)
+            float am = -INFINITY;
+            for (int k = 0; k < NB; ++k) am = fmaxf(am, sc.bst[((int64_t)b * NB + k) * 4 + 2] + a.run_scores_in[(int64_t)b * NB + k]);
+            s_amax = am; s_err = 0;
+        }
+    } else if (tid < NB) {
         const float* st = stats + ((int64_t)b * NB + tid) * BEAM_CHUNKS * 2;
         float mx = -INFINITY;
         for (int c = 0; c < BEAM_CHUNKS; ++c) mx = fmaxf(mx, st[c * 2]);
@@ -122,7 +163,9 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
         const int beam = i / (BEAM_CHUNKS * KEEP);
         const float x = cand_x[(int64_t)b * NC + i];
         const int tok = cand_i[(int64_t)b * NC + i];
-        float v = ((x - s_mx[beam]) - s_lse[beam]) + a.run_scores_in[(int64_t)b * NB + beam];
+        float v;
+        if constexpr (SAMPLE) { v = x; lpa[i] = sc.cand_a[(int64_t)b * NC + i]; }
+        else v = ((x - s_mx[beam]) - s_lse[beam]) + a.run_scores_in[(int64_t)b * NB + beam];
         if (tok == INT_MAX) v = -INFINITY;
         lpv[i] = v;
         lpi[i] = tok == INT_MAX ? INT_MAX : (int)(beam * V + tok);
@@ -147,6 +190,13 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
         for (int w = 1; w < BEAM_THREADS / 64; ++w)
             if (s_wp[w] >= 0 && (gp < 0 || cand_better(s_wv[w], s_wi[w], gv, gi))) { gv = s_wv[w]; gi = s_wi[w]; gp = s_wp[w]; }
         __syncthreads();
+        if constexpr (SAMPLE) {
+            if (tid == 0) {                                       // the draw: the key ranks, the un-noised score goes on
+                const bool ok = gp >= 0 && gv > -INFINITY && expf(lpa[gp] - s_amax) > 0.0f;
+                if (!ok) s_err = 1;
+                top_lp[r] = gp >= 0 ? lpa[gp] : -INFINITY; top_ix[r] = gp >= 0 ? gi : 0; if (gp >= 0) lpi[gp] = -1;
+            }
+        } else
         if (tid == 0) { top_lp[r] = gp >= 0 ? gv : -INFINITY; top_ix[r] = gp >= 0 ? gi : 0; if (gp >= 0) lpi[gp] = -1; }       // taken
         __syncthreads();                                   // ... before the next round scans the list
     }
@@ -225,6 +275,7 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
         if (improve_out) atomicAdd(&a.sync[1], 1);
         if (all_hits) atomicAdd(&a.sync[2], 1);
         if (all_fin_out) atomicAdd(&a.sync[3], 1);
+        if constexpr (SAMPLE) if (s_err) atomicAdd(sc.err, 1);
     }
     __syncthreads();
     // ---- (5) token rows of the new running / finished sets
@@ -255,6 +306,8 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
             atomicExch(&a.sync[0], 0);
             bool unfinished = n_improve > 0 && n_hits < (int)gridDim.x;
             if (a.early_stopping) unfinished = unfinished && n_fin < (int)gridDim.x;
+            if constexpr (SAMPLE) a.flags[0] = (unfinished ? 1 : 0) | (atomicExch(sc.err, 0) ? 2 : 0);
+            else
             a.flags[0] = unfinished ? 1 : 0;
         }
     }
@@ -294,6 +347,129 @@ extern "C" int licv_beam_step(const licv_beam_step_args* x, void* stream) {
         default: BEAM_LAUNCH(16); break;
     }
 #undef BEAM_LAUNCH
+    LICV_LAUNCH_CHECK();
+    return LICV_OK;
+}
+
+// ---- beam-search multinomial sampling: per-beam pre-pass (one 1024-lane workgroup per (question, beam)).  It evaluates the beam's
+// log-softmax statistics exactly as beam_scan_k / beam_finish_k do (32 chunks of 256 lanes, the same order of every sum), then the
+// processed scores y = ((x - max) - lse) / T with EOS suppressed, and their kept set with the device code of sample.hip (mtk = 2).
+template <int NPT>
+__global__ __launch_bounds__(SAMPLE_THREADS)
+void beam_sample_prep_k(licv_beam_step_args a, licv_sample_params p, float* __restrict__ bst, uint32_t* __restrict__ thr) {
+    __shared__ SampleSmem s;
+    __shared__ float red[SAMPLE_THREADS / 64];
+    __shared__ float cst[BEAM_CHUNKS * 2];
+    __shared__ float s_mx, s_lse;
+    const int bk = blockIdx.x, b = bk / (int)a.nb, beam = bk % (int)a.nb, tid = threadIdx.x;
+    const int g = tid / BEAM_THREADS, t = tid % BEAM_THREADS, lane = tid & 63, wave = tid >> 6;
+    const int V = (int)a.V;
+    const int64_t row = ((int64_t)b * a.q_stride_rows + (int64_t)beam * a.beam_stride_rows) * a.ld;
+    auto ld = [&](int i) { return a.logits_dtype == LICV_F32 ? reinterpret_cast<const float*>(a.logits)[row + i]
+                                                             : bf2f(reinterpret_cast<const bf16_t*>(a.logits)[row + i]); };
+    const int ch = (V + BEAM_CHUNKS - 1) / BEAM_CHUNKS;
+    constexpr int GROUPS = SAMPLE_THREADS / BEAM_THREADS;
+    for (int c0 = 0; c0 < BEAM_CHUNKS; c0 += GROUPS) {          // group g of 256 lanes: chunk c0 + g, as one beam_scan_k workgroup
+        const int c = c0 + g, i0 = c * ch, n = max(0, min(ch, V - i0));
+        float mx = -INFINITY;
+        for (int i = t; i < n; i += BEAM_THREADS) mx = fmaxf(mx, ld(i0 + i));
+        mx = wave_max(mx);
+        __syncthreads();
+        if (lane == 0) red[wave] = mx;
+        __syncthreads();
+        float gm = red[g * 4];
+        for (int w = 1; w < BEAM_THREADS / 64; ++w) gm = fmaxf(gm, red[g * 4 + w]);
+        float z = 0.f;
+        for (int i = t; i < n; i += BEAM_THREADS) z += expf(ld(i0 + i) - gm);
+        z = wave_sum(z);
+        __syncthreads();
+        if (lane == 0) red[wave] = z;
+        __syncthreads();
+        float gz = red[g * 4];
+        for (int w = 1; w < BEAM_THREADS / 64; ++w) gz = gz + red[g * 4 + w];
+        if (t == 0) { cst[c * 2] = gm; cst[c * 2 + 1] = gz; }
+    }
+    __syncthreads();
+    if (tid == 0) {                                                 // beam_finish_k (1)
+        float mx = -INFINITY;
+        for (int c = 0; c < BEAM_CHUNKS; ++c) mx = fmaxf(mx, cst[c * 2]);
+        float z = 0.f;
+        for (int c = 0; c < BEAM_CHUNKS; ++c) z += cst[c * 2 + 1] * expf(cst[c * 2] - mx);
+        s_mx = mx; s_lse = logf(z);
+    }
+    __syncthreads();
+    const float mx = s_mx, lse = s_lse;
+    const int npt = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS, base = tid * npt;
+    uint32_t kk[NPT];
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) {
+        const int i = base + j;
+        uint32_t k = 0;
+        if (j < npt && i < V) {
+            float y = ((ld(i) - mx) - lse) / p.temperature;
+            if (a.suppress_eos && i == a.eos) y = -INFINITY;
+            k = f2key(y);
+        }
+        kk[j] = k;
+    }
+    const SampleFilter f{p.temperature, p.top_k, p.top_p, p.min_p, 2};
+    float m;
+    const KeptSet S = row_filter(kk, npt, base, V, f, &m, s);
+    if (tid == 0) {
+        bst[bk * 4] = mx; bst[bk * 4 + 1] = lse; bst[bk * 4 + 2] = m; bst[bk * 4 + 3] = 0.f;
+        thr[bk * 2] = S.t; thr[bk * 2 + 1] = (uint32_t)S.c;
+    }
+}
+
+extern "C" int64_t licv_beam_sample_scratch_bytes(int64_t B, int64_t nb) {
+    return beam_scratch_floats(B, nb) * 4 + B * nb * BEAM_CHUNKS * 2 * nb * 4 + B * nb * (4 + 2) * 4 + 16;
+}
+
+extern "C" int licv_beam_sample_step(const licv_beam_step_args* x, const licv_sample_params* p, void* stream) {
+    LICV_CHECK_ARG(x && p && x->logits && x->running_in && x->finished_in && x->run_scores_in && x->fin_scores_in && x->is_fin_in && x->improve_in &&
+                   x->gen_len_in && x->running_out && x->finished_out && x->run_scores_out && x->fin_scores_out && x->is_fin_out &&
+                   x->improve_out && x->gen_len_out && x->beam_src_flat && x->next_tokens && x->flags && x->sync && x->scratch,
+                   "beam_sample_step: null pointer");
+    LICV_CHECK_ARG(x->logits_dtype == LICV_BF16 || x->logits_dtype == LICV_F32, "beam_sample_step: bad logits dtype");
+    LICV_CHECK_ARG(x->nb >= 2 && x->nb <= BEAM_MAX_NB, "beam_sample_step: num_beams %lld outside 2..%d", (long long)x->nb, BEAM_MAX_NB);
+    LICV_CHECK_ARG(x->B >= 1 && x->V >= 2 * x->nb && x->ld >= x->V && x->nb * x->V < (1ll << 31), "beam_sample_step: bad batch / vocabulary size");
+    LICV_CHECK_ARG(x->V <= (int64_t)BEAM_CHUNKS * BEAM_CHUNK_MAX && x->V <= SAMPLE_MAX_V,
+                   "beam_sample_step: vocabulary %lld above the scan's limit %d", (long long)x->V, BEAM_CHUNKS * BEAM_CHUNK_MAX);
+    LICV_CHECK_ARG(x->scratch_bytes >= licv_beam_sample_scratch_bytes(x->B, x->nb) && ((uintptr_t)x->scratch & 15) == 0,
+                   "beam_sample_step: scratch smaller than licv_beam_sample_scratch_bytes(B, nb) or misaligned");
+    LICV_CHECK_ARG(x->cur >= x->P && x->cur < x->max_len && x->P >= 1, "beam_sample_step: position %lld outside [P, max_len)", (long long)x->cur);
+    LICV_CHECK_ARG(x->running_in != x->running_out && x->finished_in != x->finished_out, "beam_sample_step: the token rows need separate in / out buffers");
+    LICV_CHECK_ARG((x->kv_rows_in == nullptr) == (x->kv_rows_out == nullptr) && (!x->kv_rows_in || (x->kv_rows_in != x->kv_rows_out && x->kv_ld > x->cur)),
+                   "beam_sample_step: the KV row table needs separate in / out buffers with rows longer than the current position");
+    LICV_CHECK_ARG(p->temperature > 0.0f, "beam_sample_step: temperature %g must be > 0", (double)p->temperature);
+    LICV_CHECK_ARG(p->top_k >= 0, "beam_sample_step: top_k %lld must be >= 0", (long long)p->top_k);
+    LICV_CHECK_ARG(p->top_p > 0.0f && p->top_p <= 1.0f, "beam_sample_step: top_p %g outside (0, 1]", (double)p->top_p);
+    LICV_CHECK_ARG(p->min_p >= 0.0f && p->min_p <= 1.0f, "beam_sample_step: min_p %g outside [0, 1]", (double)p->min_p);
+    const int64_t slots = x->B * x->nb * BEAM_CHUNKS;
+    float* stats = (float*)x->scratch;
+    float* cand_x = stats + slots * 2;
+    int* cand_i = (int*)(cand_x + slots * 2 * x->nb);
+    float* cand_a = (float*)(cand_i + slots * 2 * x->nb);
+    float* bst = cand_a + slots * 2 * x->nb;
+    uint32_t* thr = (uint32_t*)(bst + x->B * x->nb * 4);
+    int* err = (int*)(thr + x->B * x->nb * 2);
+    const BeamSampleCtx sc{bst, thr, cand_a, err, p->seed, p->temperature};
+    const dim3 sgrid((unsigned)(x->B * BEAM_CHUNKS)), grid((unsigned)x->B), block(BEAM_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (x->V <= SAMPLE_THREADS * 32) beam_sample_prep_k<32><<<dim3((unsigned)(x->B * x->nb)), dim3(SAMPLE_THREADS), 0, st>>>(*x, *p, bst, thr);
+    else beam_sample_prep_k<SAMPLE_NPT><<<dim3((unsigned)(x->B * x->nb)), dim3(SAMPLE_THREADS), 0, st>>>(*x, *p, bst, thr);
+#define BEAM_SAMPLE_LAUNCH(K) do { beam_scan_k<K, true><<<sgrid, block, 0, st>>>(*x, stats, cand_x, cand_i, sc); \
+                                   beam_finish_k<K, true><<<grid, block, 0, st>>>(*x, stats, cand_x, cand_i, sc); } while (0)
+    switch (x->nb) {
+        case 2: BEAM_SAMPLE_LAUNCH(4); break;
+        case 3: BEAM_SAMPLE_LAUNCH(6); break;
+        case 4: BEAM_SAMPLE_LAUNCH(8); break;
+        case 5: BEAM_SAMPLE_LAUNCH(10); break;
+        case 6: BEAM_SAMPLE_LAUNCH(12); break;
+        case 7: BEAM_SAMPLE_LAUNCH(14); break;
+        default: BEAM_SAMPLE_LAUNCH(16); break;
+    }
+#undef BEAM_SAMPLE_LAUNCH
     LICV_LAUNCH_CHECK();
     return LICV_OK;
 }

@@ -18,7 +18,7 @@ LAB_PATH = Path(os.environ.get("LICV_HIP_LAB_LIB", _HERE / "liblicv_hip_lab.so")
 LAB_HEADER = _HERE.parents[1] / "include" / "licv_hip_lab.h"
 
 LICV_BF16, LICV_F32 = 0, 1
-ABI_VERSION = 6          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
+ABI_VERSION = 7          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
 
 _lib = None
 _lab = None
@@ -58,6 +58,18 @@ class BeamStepArgs(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
 
 
+class SampleParams(C.Structure):
+    """licv_sample_params (include/licv_hip.h): the warpers of a sampled decode step and the Philox key."""
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int64), ("top_p", C.c_float), ("min_p", C.c_float), ("seed", C.c_uint64)]
+
+
+class SampleStepArgs(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("logits_dtype", C.c_int), ("ld", C.c_int64), ("B", C.c_int64), ("V", C.c_int64),
+                ("ids", C.c_void_p), ("ids_ld", C.c_int64), ("max_len", C.c_int64), ("cur", C.c_int64), ("P", C.c_int64),
+                ("unfinished", C.c_void_p), ("next_tokens", C.c_void_p), ("eos", C.c_int64), ("pad", C.c_int64),
+                ("suppress_eos", C.c_int), ("flags", C.c_void_p), ("sync", C.c_void_p)]
+
+
 class DecodeAttnArgs(C.Structure):
     _fields_ = [("qkv_ws", C.c_void_p), ("splits", C.c_int), ("slice_elems", C.c_int64), ("row_stride", C.c_int64),
                 ("qkv_bf16", C.c_void_p), ("ldq", C.c_int64),
@@ -90,6 +102,8 @@ def lib() -> C.CDLL:
         _lib.licv_inject_bwd_partials.argtypes = [C.c_int64]
         _lib.licv_beam_step_scratch_bytes.restype = C.c_int64
         _lib.licv_beam_step_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
+        _lib.licv_beam_sample_scratch_bytes.restype = C.c_int64
+        _lib.licv_beam_sample_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
         P, I64, F, I = C.c_void_p, C.c_int64, C.c_float, C.c_int
         sig = {
             "licv_inject_renorm_fwd": [P, I, P, P, P, I64, I64, P, P, F, P],
@@ -133,6 +147,8 @@ def lib() -> C.CDLL:
             "licv_attn_select": [I],
             "licv_attn_fwd": [C.POINTER(AttnArgs), P],
             "licv_beam_step": [C.POINTER(BeamStepArgs), P],
+            "licv_sample_step": [C.POINTER(SampleStepArgs), C.POINTER(SampleParams), P],
+            "licv_beam_sample_step": [C.POINTER(BeamStepArgs), C.POINTER(SampleParams), P],
             "licv_decode_attn": [C.POINTER(DecodeAttnArgs), P],
             "licv_embed_gather": [P, P, P, P, I64, I64, I64, I64, P],
             "licv_im2col_patches": [P, P, I64, I64, I64, I64, I64, P],

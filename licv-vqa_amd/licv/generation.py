@@ -120,10 +120,26 @@ def generate_idefics2(engine, input_ids: torch.Tensor, attention_mask: torch.Ten
     return _decode(model, engine.arch, input_ids, attention_mask, max_new_tokens=max_new_tokens, num_beams=num_beams, **kw)
 
 
+def sample_params(temperature=None, top_k=None, top_p=None, min_p=None, seed=None):
+    """The warpers of a sampled decode with transformers' defaults for what the caller leaves out (hf:generation/
+    configuration_utils.py:616-618: temperature 1.0, top_k 50, top_p 1.0, min_p None) and the Philox key."""
+    from . import _lib
+    p = _lib.SampleParams()
+    p.temperature = 1.0 if temperature is None else float(temperature)
+    p.top_k = 50 if top_k is None else int(top_k)
+    p.top_p = 1.0 if top_p is None else float(top_p)
+    p.min_p = 0.0 if min_p is None else float(min_p)
+    p.seed = (int(torch.randint(0, 2 ** 63 - 1, (1,)).item()) if seed is None else int(seed)) & (2 ** 64 - 1)
+    return p
+
+
 def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int = 5, num_beams: int = 1,
             length_penalty: float = 1.0, min_new_tokens: int = 0, early_stopping=False,
-            eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None) -> torch.Tensor:
+            eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, do_sample: bool = False,
+            temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
+            min_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
     dev = input_ids.device
+    sampling = sample_params(temperature, top_k, top_p, min_p, seed) if do_sample else None
     eos = a.eos_token_id if eos_token_id is None else eos_token_id
     pad = a.pad_token_id if pad_token_id is None else pad_token_id
     B, P = input_ids.shape
@@ -136,6 +152,17 @@ def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max
             lp = lp.clone()
             lp[..., eos] = -float("inf")
         return lp
+
+    if nb == 1 and sampling is not None:                              # ---- multinomial sampling (_sample, do_sample): csrc/sample.hip
+        state = SampleState(B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling)
+        am = attention_mask
+        while True:
+            more = state.step(logits)                                 # one device -> host read per step
+            if not more:
+                break
+            am = torch.cat([am, torch.ones((B, 1), dtype=am.dtype, device=dev)], 1)
+            logits = model.step(state.next_tokens.view(B, 1), am)
+        return state.result()
 
     if nb == 1:                                                       # ---- greedy (GenerationMixin._sample)
         seq = torch.full((B, max_len), pad, dtype=torch.long, device=dev)
@@ -166,7 +193,8 @@ def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max
     # table, which the search kernel then keeps up to date itself; the first step reads the B prefill rows directly
     model.replicate(nb)
     table = model.kv_rows() if hasattr(model, "kv_rows") and hasattr(model, "reorder_with_rows") else None
-    search = BeamSearchState(B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=table)
+    search = BeamSearchState(B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=table,
+                             sampling=sampling)
     am = attention_mask.repeat_interleave(nb, 0)
     first = True
     while True:
@@ -188,8 +216,11 @@ class BeamSearchState:
     """Device-side state of one beam search (running / finished token rows, scores, flags), advanced by `licv_beam_step`.
     Two copies of every buffer: the kernel gathers rows of the old state into the new one."""
 
-    def __init__(self, B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=None):
+    def __init__(self, B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=None,
+                 sampling=None):
         dev = input_ids.device
+        # sampling: a licv._lib.SampleParams (beam-search multinomial sampling through licv_beam_sample_step), None = beam search
+        self.sampling = sampling
         self.B, self.nb, self.P, self.max_len, self.cur = B, nb, P, max_len, P
         self.eos = -1 if eos is None else int(eos)
         self.length_penalty, self.early_stopping, self.min_new_tokens = float(length_penalty), early_stopping is True, int(min_new_tokens)
@@ -207,7 +238,10 @@ class BeamSearchState:
         self.flags = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.sync = torch.zeros((4,), dtype=torch.int32, device=dev)
         from . import _lib
-        self.scratch = torch.empty((int(_lib.lib().licv_beam_step_scratch_bytes(B, nb)),), dtype=torch.uint8, device=dev)
+        if sampling is None:
+            self.scratch = torch.empty((int(_lib.lib().licv_beam_step_scratch_bytes(B, nb)),), dtype=torch.uint8, device=dev)
+        else:                                                  # (holds an error counter that must start at zero)
+            self.scratch = torch.zeros((int(_lib.lib().licv_beam_sample_scratch_bytes(B, nb)),), dtype=torch.uint8, device=dev)
         # optional: the KV cache's row table (B*nb, cache max_len) int32, ping-ponged like the rest of the state
         self.kv_rows = kv_rows
         self._kv_rows_next = torch.empty_like(kv_rows) if kv_rows is not None else None
@@ -236,14 +270,61 @@ class BeamSearchState:
         if self.kv_rows is not None:
             assert self.kv_rows.dtype == torch.int32 and self.kv_rows.is_contiguous() and self.kv_rows.shape[0] == self.B * self.nb
             a.kv_rows_in, a.kv_rows_out, a.kv_ld = self.kv_rows.data_ptr(), self._kv_rows_next.data_ptr(), self.kv_rows.shape[1]
-        check(_lib.lib().licv_beam_step(C.byref(a), _stream(logits)))
+        if self.sampling is None:
+            check(_lib.lib().licv_beam_step(C.byref(a), _stream(logits)))
+        else:
+            check(_lib.lib().licv_beam_sample_step(C.byref(a), C.byref(self.sampling), _stream(logits)))
         if self.kv_rows is not None:
             self.kv_rows, self._kv_rows_next = self._kv_rows_next, self.kv_rows
         self.state = [dst, src]
         self.cur += 1
-        return bool(int(self.flags[0]))
+        f = int(self.flags[0])
+        if f & 2:
+            raise ValueError("beam-search sampling: a question has fewer than 2 * num_beams candidates of non-zero probability "
+                             "(torch.multinomial raises here too); raise top_k / top_p or lower num_beams")
+        return bool(f & 1)
 
     def result(self) -> torch.Tensor:
         st = self.state[0]
         out_len = self.P + int(st["gen_len"][:, 0].max())
         return st["finished"][:, 0, :out_len]
+
+
+class SampleState:
+    """Device-side state of multinomial sampling without beams (hf GenerationMixin._sample with do_sample=True), advanced by
+    `licv_sample_step`: the running (B, max_len) id buffer, the unfinished flags and the loop flag."""
+
+    def __init__(self, B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling):
+        dev = input_ids.device
+        self.B, self.P, self.max_len, self.cur = B, P, max_len, P
+        self.eos = -1 if eos is None else int(eos)
+        self.pad = int(pad) if pad is not None else (self.eos if self.eos >= 0 else 0)
+        self.min_new_tokens, self.sampling = int(min_new_tokens), sampling
+        self.seq = torch.full((B, max_len), self.pad, dtype=torch.long, device=dev)
+        self.seq[:, :P] = input_ids
+        self.unfinished = torch.ones((B,), dtype=torch.uint8, device=dev)
+        self.next_tokens = torch.empty((B,), dtype=torch.long, device=dev)
+        self.flags = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self.sync = torch.zeros((2,), dtype=torch.int32, device=dev)
+
+    def step(self, logits: torch.Tensor) -> bool:
+        """logits: (B, V) rows (bf16 or fp32, row stride = stride(0)).  Returns whether decoding continues (reads one int32 back)."""
+        import ctypes as C
+        from . import _lib
+        from .ops import _dt, _stream, check
+        assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == self.B
+        a = _lib.SampleStepArgs()
+        a.logits, a.logits_dtype, a.ld = logits.data_ptr(), _dt(logits), logits.stride(0)
+        a.B, a.V = self.B, logits.shape[1]
+        a.ids, a.ids_ld = self.seq.data_ptr(), self.seq.stride(0)
+        a.max_len, a.cur, a.P = self.max_len, self.cur, self.P
+        a.unfinished, a.next_tokens = self.unfinished.data_ptr(), self.next_tokens.data_ptr()
+        a.eos, a.pad = self.eos, self.pad
+        a.suppress_eos = 1 if (self.min_new_tokens > 0 and self.cur - self.P < self.min_new_tokens and self.eos >= 0) else 0
+        a.flags, a.sync = self.flags.data_ptr(), self.sync.data_ptr()
+        check(_lib.lib().licv_sample_step(C.byref(a), C.byref(self.sampling), _stream(logits)))
+        self.cur += 1
+        return bool(int(self.flags[0]))
+
+    def result(self) -> torch.Tensor:
+        return self.seq[:, :self.cur]

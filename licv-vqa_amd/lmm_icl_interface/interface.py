@@ -217,16 +217,32 @@ class IdeficsInterface(LMMInterface):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_attention_mask=None,
                  max_new_tokens=20, num_beams=1, length_penalty=1.0, min_new_tokens=0, early_stopping=False,
-                 eos_token_id=None, pad_token_id=None, do_sample=False, **_):
-        if do_sample:
-            raise NotImplementedError("sampling is not part of the reference's inference path")
+                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None, **kw):
+        sampling = _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, kw)
         return native_generate(self.engine, input_ids.to(self._device), attention_mask.to(self._device),
                                pixel_values.to(self._device), self._image_mask(input_ids, pixel_values, image_attention_mask),
                                max_new_tokens=max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
                                min_new_tokens=min_new_tokens, early_stopping=early_stopping,
                                eos_token_id=eos_token_id if eos_token_id is not None else getattr(self.tokenizer, "eos_token_id", None),
                                pad_token_id=pad_token_id if pad_token_id is not None else getattr(self.tokenizer, "pad_token_id", None),
-                               **self._hooks())
+                               **sampling, **self._hooks())
+
+
+# transformers' sampling warpers the native path does not build (hf:generation/utils.py _get_logits_processor): with do_sample they
+# raise instead of being dropped
+_UNBUILT_WARPERS = ("typical_p", "top_h", "epsilon_cutoff", "eta_cutoff")
+
+
+def _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, rest):
+    """generate kwargs -> licv.generation._decode sampling kwargs (do_sample=True: Philox-seeded kernels, seeded from torch's default
+    CPU generator so that torch.manual_seed reproduces a run)."""
+    if not do_sample:
+        return {}
+    for k in _UNBUILT_WARPERS:
+        if rest.get(k) is not None:
+            raise NotImplementedError(f"generate(do_sample=True, {k}=...): the {k} warper is not built on the native path")
+    seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+    return dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
 
 
 class Idefics2Interface(IdeficsInterface):
@@ -278,9 +294,8 @@ class Idefics2Interface(IdeficsInterface):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, pixel_attention_mask=None,
                  max_new_tokens=20, num_beams=1, length_penalty=1.0, min_new_tokens=0, early_stopping=False,
-                 eos_token_id=None, pad_token_id=None, do_sample=False, **_):
-        if do_sample:
-            raise NotImplementedError("sampling is not part of the reference's inference path")
+                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None, **kw):
+        sampling = _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, kw)
         from licv.generation import generate_idefics2
         dev = self._device
         return generate_idefics2(self.engine, input_ids.to(dev), attention_mask.to(dev),
@@ -290,4 +305,4 @@ class Idefics2Interface(IdeficsInterface):
                                  min_new_tokens=min_new_tokens, early_stopping=early_stopping,
                                  eos_token_id=eos_token_id if eos_token_id is not None else getattr(self.tokenizer, "eos_token_id", None),
                                  pad_token_id=pad_token_id if pad_token_id is not None else getattr(self.tokenizer, "pad_token_id", None),
-                                 **self._hooks())
+                                 **sampling, **self._hooks())
