@@ -23,8 +23,9 @@ extern "C" {
 /* Bumped whenever an entry point is added, removed or changes its arguments; licv/_lib.py holds the same constant and refuses a
  * library that answers anything else.  1 = round 1; 2 = rounds 2-3 (fp8, split-K slices, runner, front-end, backward, image input);
  * 3-6 = round 4 (lab library split off; weight-streaming GEMM; beam scoring; decode-step fusion; backward options; RMSNorm backward
- * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step). */
-#define LICV_ABI_VERSION 7
+ * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step); 8 = RICE retrieval
+ * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu). */
+#define LICV_ABI_VERSION 8
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
 enum { LICV_OK = 0, LICV_E_BADARG = -1, LICV_E_UNSUPPORTED = -2, LICV_E_HIP = -3 };
@@ -481,6 +482,32 @@ int licv_kl_rows_dtemp(const void* stu_logits, const void* tea_logits, int dtype
 int licv_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t n_group0,
                     float lr0, float lr1, float beta1, float beta2, float eps, float weight_decay,
                     int64_t step, float grad_scale, void* stream);
+
+/* ---- RICE retrieval (ref:icv_src/utils/mm_topk_retriver.py: CLIP features -> faiss.IndexFlatIP(dim).search(queries, k)) ----
+ * Exact flat inner-product search: for each of Q query rows the k index rows (of N) with the largest fp32 inner product.
+ *   - scores are fp32 products accumulated in fp32 on the fp32-input MFMA, the whole sum over D in one fixed order (no split over D);
+ *     the score of a (query row, index row) pair depends on those two rows only - the same bits wherever the index row sits and
+ *     whatever Q, N and the tiling are;
+ *   - each output row is sorted by (score descending, index ascending): EQUAL SCORES RESOLVE TO THE LOWEST INDEX (faiss leaves ties
+ *     unspecified; this library defines them).  -0 and +0 are equal.  A NaN score is LOWER THAN EVERY NUMBER (below -inf) and is
+ *     returned as NaN if it has to be (rows are L2-normalised upstream, so none is expected);
+ *   - the Q x N score matrix is never stored: each workgroup keeps a running top-k per query over the index tiles of its chunk and
+ *     writes k (score, index) entries per (query, chunk) to the workspace, a second kernel merges the chunks in chunk order.  No
+ *     atomics: results are bit-reproducible.  Workspace: Q * chunks * k * 8 bytes with chunks <= 128 (licv_topk_ip_workspace).
+ * Supported: 1 <= k <= 64, k <= N, D % 4 == 0, 4 <= D <= 1024, Q >= 1, N < 2^31 - 128; ldq / ldx >= D and multiples of 4, queries /
+ * index 16-byte aligned.  Anything else is LICV_E_BADARG (nothing is clamped).  out_idx (Q, k) int64 (as faiss returns them), out_score
+ * (Q, k) fp32, both dense. */
+int licv_topk_ip_workspace(int64_t Q, int64_t N, int64_t D, int64_t k, int64_t* bytes);
+int licv_topk_ip(const float* queries, int64_t ldq, const float* index, int64_t ldx, int64_t Q, int64_t N, int64_t D, int64_t k,
+                 int64_t* out_idx, float* out_score, void* workspace, int64_t workspace_bytes, void* stream);
+/* features /= features.norm(dim=-1, keepdim=True) (ref:icv_src/utils/mm_topk_retriver.py, before the features go to faiss): dense
+ * (rows, dim) bf16 or fp32 in, fp32 out; the norm is one fp32 value per row (rounded once from an fp64 sum of squares), the division
+ * is IEEE fp32.  out may alias x when x is fp32. */
+int licv_l2_normalize_rows(const void* x, int x_dtype, float* out, int64_t rows, int64_t dim, void* stream);
+/* QuickGELU (hf:activations.py QuickGELUActivation, CLIP's hidden_act) in place on a (rows, dim) bf16 view with row stride ld:
+ * y = bf16(x * bf16(sigmoid(bf16(1.702 x)))), each step rounded to bf16 as the unfused torch ops round.  Columns dim..ld-1 are not
+ * touched. */
+int licv_quick_gelu(void* x_bf16, int64_t rows, int64_t dim, int64_t ld, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,139 @@
+"""RICE retrieval (retrieval by image similarity) behind the reference's interface: `MMTopkRetriever` of
+ref:icv_src/utils/mm_topk_retriver.py (the reference's spelling of the file name), as ref:inference.py:185-199 constructs it and
+:204 calls it.  Same constructor surface, attributes and cache-file layout; underneath, the CLIP image tower runs on the native
+engine (licv/clip_engine.py) and the exact inner-product search that the reference hands to faiss.IndexFlatIP is one fused HIP kernel
+(licv_topk_ip).  Equal scores resolve to the lowest index (faiss leaves ties unspecified).
+
+What differs, on purpose: there is no network, so `clip_model_name` has to resolve to a local directory; the text tower and the
+tokenizer are out of scope, so a mode with a "t" in it works from a cache file only; `cache_file=None` computes without saving."""
+from __future__ import annotations
+
+import os
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)               # hf:utils/constants.py OPENAI_CLIP_MEAN / OPENAI_CLIP_STD
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+MAX_WORKERS = 16
+
+
+def resize_center_crop_u8(img, size: int) -> np.ndarray:
+    """hf CLIPImageProcessor up to its rescale step, on the host with PIL: RGB, shortest edge -> size (bicubic; the long edge is
+    int(size * long / short)), centre crop size x size.  -> (size, size, 3) uint8."""
+    from PIL import Image
+    if not isinstance(img, Image.Image):
+        img = Image.fromarray(np.asarray(img))
+    img = img.convert("RGB")
+    w, h = img.size
+    if w <= h:
+        nw, nh = size, int(size * h / w)
+    else:
+        nw, nh = int(size * w / h), size
+    if (nw, nh) != (w, h):
+        img = img.resize((nw, nh), resample=Image.BICUBIC)
+    left, top = (nw - size) // 2, (nh - size) // 2
+    return np.asarray(img.crop((left, top, left + size, top + size)), dtype=np.uint8)
+
+
+def resolve_clip_dir(name: str) -> Path:
+    """`name` as given, or under $MODEL_CPK_DIR (the reference's variable for model directories): the first that is a directory."""
+    tried = [Path(name)]
+    root = os.environ.get("MODEL_CPK_DIR")
+    if root:
+        tried += [Path(root) / name, Path(root) / Path(name).name]
+    for p in tried:
+        if p.is_dir():
+            return p
+    raise FileNotFoundError(f"CLIP model {name!r} is not a local directory (config.json + *.safetensors; there is no network to fetch it). "
+                            f"Tried: {', '.join(str(p) for p in tried)}" + ("" if root else " (MODEL_CPK_DIR is not set)"))
+
+
+class MMTopkRetriever:
+    def __init__(self, index_ds: Sequence[dict], test_ds: Sequence[dict], clip_model_name: Optional[str] = "openai/clip-vit-base-patch32",
+                 mode: Optional[str] = "i2t", index_field: Optional[str] = "text", test_field: Optional[str] = "image",
+                 batch_size: Optional[int] = 1, num_workers: Optional[int] = 0, cache_file: Optional[str] = None, device: str = "cuda",
+                 reversed_order: Optional[bool] = False, *, clip_weights=None, img_processor: Optional[Callable] = None) -> None:
+        """As the reference class.  Keyword-only extras: `clip_weights` = (ClipVisionArch, state dict) of a tower held in memory
+        (then clip_model_name is a label only); `img_processor` = callable, list of images -> (n, 3, S, S) tensor, replacing the
+        built-in CLIPImageProcessor restatement."""
+        self.index_ds, self.test_ds = index_ds, test_ds
+        self.clip_model_name = clip_model_name
+        self.device = device
+        self.batch_size = max(1, int(batch_size or 1))
+        self.num_workers = max(0, min(int(num_workers or 0), MAX_WORKERS))
+        self.mode = mode
+        self.index_field, self.test_field = index_field, test_field
+        self.reversed_order = reversed_order
+        self._clip_weights, self._img_processor = clip_weights, img_processor
+        self._index_dev = self._test_dev = None
+        if cache_file is None or not os.path.exists(cache_file):
+            self.create_index(cache_file)
+        else:
+            features = torch.load(cache_file, weights_only=False)       # the reference's layout: numpy arrays in a pickled dict
+            self.index_features = np.ascontiguousarray(features["index_features"], dtype=np.float32)
+            self.test_features = np.ascontiguousarray(features["test_features"], dtype=np.float32)
+
+    # ------------------------------------------------------------------------------------------ features
+    def create_index(self, cache_file: Optional[str]) -> None:
+        index_enc, test_enc = self.mode.split("2")[1], self.mode.split("2")[0]
+        if "t" in (index_enc, test_enc):
+            raise NotImplementedError(f"mode {self.mode!r} needs the CLIP text tower, which this package does not have: compute 'i2i' "
+                                      f"features, or pass a cache_file written by the reference")
+        from licv.clip_engine import ClipVisionEngine, load_clip_vision
+        arch, sd = self._clip_weights if self._clip_weights is not None else load_clip_vision(resolve_clip_dir(self.clip_model_name))
+        self.vision_encoder = ClipVisionEngine(arch, sd, self.device)
+        index_dev = self.encode_img(self.index_ds, self.index_field)
+        test_dev = self.encode_img(self.test_ds, self.test_field)
+        self._index_dev, self._test_dev = index_dev, test_dev
+        self.index_features, self.test_features = index_dev.cpu().numpy(), test_dev.cpu().numpy()
+        if cache_file is not None:
+            torch.save({"index_features": self.index_features, "test_features": self.test_features,
+                        "meta_info": {"clip_model_name": self.clip_model_name, "mode": self.mode, "index_field": self.index_field,
+                                      "test_field": self.test_field}}, cache_file)
+        del self.vision_encoder
+
+    def _pixel_values(self, images: list, pool) -> torch.Tensor:
+        if self._img_processor is not None:
+            return self._img_processor(images)
+        from licv import frontend
+        S = self.vision_encoder.arch.image_size
+        crop = lambda im: resize_center_crop_u8(im, S)
+        u8 = np.stack(list(pool.map(crop, images)) if pool is not None else [crop(im) for im in images])
+        return frontend.preprocess_images(torch.from_numpy(u8).to(self.device), mean=CLIP_MEAN, std=CLIP_STD)[0]
+
+    @torch.inference_mode()
+    def encode_img(self, ds: Sequence[dict], img_field: str) -> torch.Tensor:
+        """Every image of `ds` through the tower, `batch_size` at a time, one pass per batch -> (len(ds), dim) fp32 unit rows on the
+        device."""
+        n = len(ds)
+        out = None
+        pool = ThreadPoolExecutor(self.num_workers) if self.num_workers > 0 else None
+        try:
+            for b0 in range(0, n, self.batch_size):
+                images = [ds[i][img_field] for i in range(b0, min(n, b0 + self.batch_size))]
+                feats = self.vision_encoder.encode(self._pixel_values(images, pool))
+                if out is None:
+                    out = torch.empty((n, feats.shape[1]), dtype=torch.float32, device=feats.device)
+                out[b0:b0 + len(images)] = feats
+        finally:
+            if pool is not None:
+                pool.shutdown()
+        if out is None:
+            raise ValueError("encode_img: empty dataset")
+        return out
+
+    # ------------------------------------------------------------------------------------------ search
+    def retrieve(self, ice_num: int) -> List[List[int]]:
+        """For every test row the `ice_num` index rows of largest inner product, best first (reversed_order: best last)."""
+        from licv import ops
+        if self._index_dev is None:                                      # features came from a cache file: the device is first touched here
+            self._index_dev = torch.from_numpy(self.index_features).to(self.device)
+            self._test_dev = torch.from_numpy(self.test_features).to(self.device)
+        idx_list = ops.topk_ip(self._test_dev, self._index_dev, int(ice_num))[0].tolist()
+        if self.reversed_order:
+            idx_list = [list(reversed(i)) for i in idx_list]
+        return idx_list

@@ -1,8 +1,10 @@
-"""Mirror of the hot-path functions of the reference's `inference.py` (ref:inference.py:246-321): `generate_answers` — ICV
-scaling, hooked generate, prompt strip, `batch_decode` — and the `icv_inference` batching loop around it, on the native
-interfaces.  The Hydra `main`, dataset loading and the ICL baseline are out of scope; a maintainer who
-runs the reference's own `inference.py` against this package (`PYTHONPATH=licv-vqa_amd`) gets the same two functions from the
-reference file itself, driving the same `LearnableICVInterventionLMM.generate`."""
+"""Mirror of the hot-path functions of the reference's `inference.py` (ref:inference.py:206-211, 246-377): `generate_answers` — ICV
+scaling, hooked generate, prompt strip, `batch_decode` — the `icv_inference` batching loop around it, and the ICL baseline's
+`icl_inference` (few-shot prompts whose demonstrations come from `ice_idx_list`: drawn at random, `random_ice_idx_list`, or by RICE,
+`icv_src.utils.mm_topk_retriver.MMTopkRetriever`), on the native interfaces.  The Hydra `main` and dataset loading are out of scope
+(SURVEY.md §2 rows 13-14); a maintainer who runs the reference's own `inference.py` against this package
+(`PYTHONPATH=licv-vqa_amd`) gets the same functions from the reference file itself, driving the same
+`LearnableICVInterventionLMM.generate` and the same retriever class."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, List, Optional, Sequence
@@ -53,6 +55,43 @@ def icv_inference(val_ds: Sequence[dict], icv_model, prompt_manager, processor, 
         query_inputs = {k: v.to(icv_model.lmm.device) for k, v in query_inputs.items()}
         generated = generate_answers(inputs=query_inputs, model=icv_model, processor=processor, generate_kwargs=generate_kwargs,
                                      in_context_vector=in_context_vector, alpha=alpha)
+        for i in range(len(batch)):
+            rec = dict(batch[i])
+            rec.pop("image")
+            results[index] = {"prediction": generated[i], **rec}
+            index += 1
+    return results
+
+
+def random_ice_idx_list(n_train: int, n_val: int, shot_num: int, rng=None) -> List[List[int]]:
+    """ref:inference.py:206-211, the branch without RICE: for every test sample `shot_num` distinct training indices drawn without
+    replacement.  `rng`: a `random.Random` (default: the module-level generator, as the reference uses it)."""
+    import random
+    rng = random if rng is None else rng
+    pool = list(range(n_train))
+    return [rng.sample(pool, shot_num) for _ in range(n_val)]
+
+
+@torch.inference_mode()
+def icl_inference(train_ds: Sequence[dict], val_ds: Sequence[dict], ice_idx_list: Sequence[Sequence[int]], model, prompt_manager,
+                  processor, bs: int, generate_kwargs: dict, instruction: str = "") -> Dict[int, dict]:
+    """ref:inference.py:323-377, the in-context-learning baseline: prompts [instruction?, (ice image, ice text with label) x shots,
+    query image, "Question: ... Short answer:"] with the demonstrations of sample i taken from train_ds in the order of
+    ice_idx_list[i], in chunks of `bs`, plain generate (no vector: the hooks get icv=None), one result record per sample.  As in
+    `icv_inference` a short last chunk is still `bs` prompts wide and the caller's samples are not mutated."""
+    results: Dict[int, dict] = {}
+    index = 0
+    for batch in _chunks(val_ds, bs):
+        prompts = [[instruction] if instruction else [] for _ in range(bs)]
+        sub_ice_idx_list = ice_idx_list[index:index + bs]
+        for i, sample in enumerate(batch):
+            for ice_idx in sub_ice_idx_list[i]:
+                ice = train_ds[int(ice_idx)]
+                prompts[i].extend([ice["image"], prompt_manager.gen_ice_text_with_label(ice, add_sep_token=True)])
+            prompts[i].extend([sample["image"], prompt_manager.gen_query_text_without_label(sample)])
+        inputs = processor.prepare_input(prompts)
+        inputs = {k: v.to(model.lmm.device) for k, v in inputs.items()}
+        generated = generate_answers(inputs=inputs, model=model, processor=processor, generate_kwargs=generate_kwargs)
         for i in range(len(batch)):
             rec = dict(batch[i])
             rec.pop("image")

@@ -18,7 +18,7 @@ LAB_PATH = Path(os.environ.get("LICV_HIP_LAB_LIB", _HERE / "liblicv_hip_lab.so")
 LAB_HEADER = _HERE.parents[1] / "include" / "licv_hip_lab.h"
 
 LICV_BF16, LICV_F32 = 0, 1
-ABI_VERSION = 7          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
+ABI_VERSION = 8          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
 
 _lib = None
 _lab = None
@@ -164,6 +164,10 @@ def lib() -> C.CDLL:
             "licv_kl_rows_fwd": [P, P, I, P, P, I64, I64, I64, I64, F, F, P, P],
             "licv_kl_rows_dtemp": [P, P, I, P, P, I64, I64, I64, I64, F, F, P, P],
             "licv_adamw_step": [P, P, P, P, I64, I64, F, F, F, F, F, F, I64, F, P],
+            "licv_topk_ip_workspace": [I64, I64, I64, I64, P],
+            "licv_topk_ip": [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, P],
+            "licv_l2_normalize_rows": [P, I, P, I64, I64, P],
+            "licv_quick_gelu": [P, I64, I64, I64, P],
         }
         for name, args in sig.items():
             fn = getattr(_lib, name)

@@ -193,3 +193,66 @@ PRESETS = {"idefics2-8b": IDEFICS2_8B, "idefics2-tiny": IDEFICS2_TINY, "idefics2
 
 def idefics_arch(name: str) -> IdeficsArch:
     return PRESETS[name]
+
+
+# ------------------------------------------------------------------------------------------ CLIP image tower (RICE retrieval)
+CLIP_HIDDEN_ACTS = ("quick_gelu", "gelu")
+
+
+@dataclass(frozen=True)
+class ClipVisionArch:
+    """hf:clip/configuration_clip.py CLIPVisionConfig (+ projection_dim): the image tower the reference's retriever encodes with
+    (ref:icv_src/utils/mm_topk_retriver.py, `openai/clip-vit-base-patch32`).  Read from a config object or a config.json dict."""
+    hidden_size: int = 768
+    intermediate_size: int = 3072
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    image_size: int = 224
+    patch_size: int = 32
+    projection_dim: int = 512
+    layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"
+
+    def __post_init__(self):
+        if self.hidden_act not in CLIP_HIDDEN_ACTS:
+            raise ValueError(f"CLIP hidden_act {self.hidden_act!r} is not supported (one of {CLIP_HIDDEN_ACTS})")
+        if self.hidden_size % self.num_attention_heads or self.image_size % self.patch_size:
+            raise ValueError("CLIP vision config: hidden_size % num_attention_heads and image_size % patch_size must be 0")
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_attention_heads
+
+    @property
+    def tokens(self) -> int:
+        return (self.image_size // self.patch_size) ** 2 + 1
+
+    def to_dict(self):
+        return asdict(self)
+
+    @staticmethod
+    def from_hf(cfg) -> "ClipVisionArch":
+        """From a transformers CLIPVisionConfig / CLIPConfig, or the dict of a config.json (a full CLIPModel's config keeps the tower
+        under `vision_config` and projection_dim at the top level)."""
+        get = (lambda o, k, d=None: o.get(k, d)) if isinstance(cfg, dict) else (lambda o, k, d=None: getattr(o, k, d))
+        vis = get(cfg, "vision_config")
+        proj = get(cfg, "projection_dim")
+        if vis is not None:
+            get_v = (lambda k, d=None: vis.get(k, d)) if isinstance(vis, dict) else (lambda k, d=None: getattr(vis, k, d))
+        else:
+            get_v = lambda k, d=None: get(cfg, k, d)
+        kw = {}
+        for f in ("hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "image_size", "patch_size",
+                  "layer_norm_eps", "hidden_act"):
+            v = get_v(f)
+            if v is None:
+                raise KeyError(f"CLIP vision config lacks {f!r}")
+            kw[f] = v
+        if proj is None:
+            proj = get_v("projection_dim")
+        if proj is None:
+            raise KeyError("CLIP config lacks 'projection_dim'")
+        return ClipVisionArch(projection_dim=int(proj), **kw)
+
+
+CLIP_VIT_B32 = ClipVisionArch()           # the public openai/clip-vit-base-patch32 numbers: bench / full-width tests without a checkpoint

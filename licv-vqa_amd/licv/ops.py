@@ -657,3 +657,46 @@ def kl_rows_bwd(stu, tea, stu_rows, tea_rows, vocab, temperature, eps, upstream=
     check(_lib.lib().licv_kl_rows_bwd(_p(stu), _p(tea), _dt(stu), _p(stu_rows), _p(tea_rows), n, vocab, stu.stride(0), tea.stride(0),
                                       float(temperature), float(eps), float(upstream), _p(upstream_dev), _p(grad), ld, _stream(stu)))
     return grad
+
+
+# ------------------------------------------------------------------------------------------ retrieval (RICE)
+def topk_ip(q: torch.Tensor, x: torch.Tensor, k: int, ldq: Optional[int] = None, ldx: Optional[int] = None):
+    """Exact inner-product search (faiss.IndexFlatIP.search): q (Q, D) and x (N, D) fp32 on the device (row strides ldq / ldx, default
+    the tensors' own) -> (idx (Q, k) int64, score (Q, k) fp32), rows sorted by (score descending, index ascending)."""
+    assert q.dtype == torch.float32 and x.dtype == torch.float32 and q.dim() == 2 and x.dim() == 2 and q.shape[1] == x.shape[1]
+    assert q.stride(1) == 1 and x.stride(1) == 1, "topk_ip: rows must be contiguous"
+    Q, D = q.shape
+    N = x.shape[0]
+    ldq = q.stride(0) if ldq is None else ldq
+    ldx = x.stride(0) if ldx is None else ldx
+    nb = C.c_int64(0)
+    check(_lib.lib().licv_topk_ip_workspace(Q, N, D, k, C.byref(nb)))
+    ws = _workspace(q.device, nb.value)
+    idx = torch.empty((Q, k), dtype=torch.int64, device=q.device)
+    score = torch.empty((Q, k), dtype=torch.float32, device=q.device)
+    _timed("gemm", 2.0 * Q * N * D, lambda: check(_lib.lib().licv_topk_ip(
+        _p(q), ldq, _p(x), ldx, Q, N, D, k, _p(idx), _p(score), _p(ws), ws.numel(), _stream(q))), label=("topk_ip", Q, N, D, k))
+    return idx, score
+
+
+def l2_normalize_rows(x: torch.Tensor) -> torch.Tensor:
+    """x (..., dim) bf16 / fp32 contiguous -> x / ||x|| per row, fp32."""
+    assert x.is_contiguous()
+    dim = x.shape[-1]
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(_lib.lib().licv_l2_normalize_rows(_p(x), _dt(x), _p(out), x.numel() // dim, dim, _stream(x)))
+    return out
+
+
+def quick_gelu_(x: torch.Tensor, rows: Optional[int] = None, dim: Optional[int] = None, ld: Optional[int] = None) -> torch.Tensor:
+    """In place x * sigmoid(1.702 x) on a bf16 (rows, dim) view with row stride ld (default: x as a dense 2-d tensor)."""
+    assert x.dtype == torch.bfloat16
+    if dim is None:
+        assert x.is_contiguous()
+        dim = x.shape[-1]
+        rows, ld = x.numel() // dim, dim
+    check(_lib.lib().licv_quick_gelu(_p(x), rows, dim, ld, _stream(x)))
+    return x
+
+
+quick_gelu = quick_gelu_

@@ -14,7 +14,7 @@ from typing import Dict, Optional
 
 import torch
 
-from .config import Idefics2Arch, IdeficsArch
+from .config import ClipVisionArch, Idefics2Arch, IdeficsArch
 
 
 def _randn(shape, std, gen, device, dtype, mean=0.0):
@@ -333,3 +333,39 @@ def synth_vqa_batch_idefics2(arch: Idefics2Arch, batch: int, seq_len: int, n_ima
             pix[b, k, :, :, ww:] = 0.0
     return {"input_ids": ids.to(device), "attention_mask": att.to(device), "pixel_values": pix.to(dtype).to(device),
             "pixel_attention_mask": pam.to(device)}
+
+
+def synth_clip_vision_weights(arch: ClipVisionArch, seed: int = 426, dtype=torch.bfloat16, device="cpu") -> Dict[str, torch.Tensor]:
+    """Random-init CLIP image tower under the key names of hf CLIPVisionModelWithProjection (hf:clip/modeling_clip.py), the same
+    distributions as the LMM generators: linear ~N(0, 0.02), norm weights ~1 + N(0, 0.1), biases ~N(0, 0.02), class embedding ~N(0, 1)."""
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev if dev.type == "cuda" else "cpu")
+    gen.manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def lin(name, out_f, in_f, bias=False):
+        sd[name + ".weight"] = _randn((out_f, in_f), 0.02, gen, dev, dtype)
+        if bias:
+            sd[name + ".bias"] = _randn((out_f,), 0.02, gen, dev, dtype)
+
+    def norm(name, dim):
+        sd[name + ".weight"] = _randn((dim,), 0.1, gen, dev, dtype, mean=1.0)
+        sd[name + ".bias"] = _randn((dim,), 0.02, gen, dev, dtype)
+
+    a, E = arch, arch.hidden_size
+    vp = "vision_model."
+    sd[vp + "embeddings.class_embedding"] = _randn((E,), 1.0, gen, dev, dtype)
+    sd[vp + "embeddings.patch_embedding.weight"] = _randn((E, 3, a.patch_size, a.patch_size), 0.02, gen, dev, dtype)
+    sd[vp + "embeddings.position_embedding.weight"] = _randn((a.tokens, E), 0.02, gen, dev, dtype)
+    norm(vp + "pre_layrnorm", E)
+    for i in range(a.num_hidden_layers):
+        p = f"{vp}encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            lin(p + "self_attn." + n, E, E, True)
+        norm(p + "layer_norm1", E)
+        lin(p + "mlp.fc1", a.intermediate_size, E, True)
+        lin(p + "mlp.fc2", E, a.intermediate_size, True)
+        norm(p + "layer_norm2", E)
+    norm(vp + "post_layernorm", E)
+    lin("visual_projection", a.projection_dim, E)
+    return sd

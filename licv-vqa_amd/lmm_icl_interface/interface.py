@@ -154,16 +154,12 @@ class IdeficsInterface(LMMInterface):
 
     @staticmethod
     def _load_checkpoint(path: Path, tokenizer, processor, arch_cls=IdeficsArch):
-        from safetensors.torch import load_file
         from transformers import AutoConfig
+        from licv.checkpoint import read_safetensors_dir
         if not path.is_dir():
             raise FileNotFoundError(f"{path} is not a local checkpoint directory (no network access to fetch one)")
         arch = arch_cls.from_hf(AutoConfig.from_pretrained(path))
-        sd = {}
-        for f in sorted(path.glob("*.safetensors")):
-            sd.update(load_file(str(f)))
-        if not sd:
-            raise FileNotFoundError(f"no *.safetensors shards under {path}")
+        sd = read_safetensors_dir(path)
         if processor is None:
             try:
                 from transformers import AutoProcessor
