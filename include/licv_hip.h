@@ -24,8 +24,8 @@ extern "C" {
  * library that answers anything else.  1 = round 1; 2 = rounds 2-3 (fp8, split-K slices, runner, front-end, backward, image input);
  * 3-6 = round 4 (lab library split off; weight-streaming GEMM; beam scoring; decode-step fusion; backward options; RMSNorm backward
  * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step); 8 = RICE retrieval
- * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu). */
-#define LICV_ABI_VERSION 8
+ * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu); 9 = image resize on the device (licv_resize_images). */
+#define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
 enum { LICV_OK = 0, LICV_E_BADARG = -1, LICV_E_UNSUPPORTED = -2, LICV_E_HIP = -3 };
@@ -508,6 +508,44 @@ int licv_l2_normalize_rows(const void* x, int x_dtype, float* out, int64_t rows,
  * y = bf16(x * bf16(sigmoid(bf16(1.702 x)))), each step rounded to bf16 as the unfused torch ops round.  Columns dim..ld-1 are not
  * touched. */
 int licv_quick_gelu(void* x_bf16, int64_t rows, int64_t dim, int64_t ld, void* stream);
+
+/* ---- image resize on the device, bit-equal to Pillow (Image.resize with BICUBIC / BILINEAR on 8-bit RGB), which is what transformers'
+ * PIL-backed image processors call (ref:icv_src/utils/mm_topk_retriver.py -> hf CLIPImageProcessor: shortest-edge resize + centre crop;
+ * ref:icv_src/icv_datamodule.py -> the Idefics / Idefics2 processors).  THE DEFINITION IS Pillow's src/libImaging/Resample.c:
+ * precompute_coeffs + normalize_coeffs_8bpc give, per output index, a first source index, a tap count and `ksize` fixed-point
+ * coefficients with 22 fractional bits; ImagingResampleHorizontal_8bpc then ImagingResampleVertical_8bpc apply them,
+ *     byte = clip8((2^21 + sum_k pixel[xmin + k] * coef[k]) >> 22)     (int32 accumulator, arithmetic shift, clamp to 0..255),
+ * the horizontal result rounded to uint8 before the vertical pass reads it, each pass only where that axis changes size.  The
+ * coefficients are computed on the HOST in IEEE double (licv.frontend.resample_plan) and uploaded; the passes are integer arithmetic,
+ * so the bytes equal Pillow's.
+ *
+ * One call resizes a ragged batch.  src: packed RGB uint8 rows (HWC), image i at byte src_offset + y * src_ld_bytes + x0_bytes + 3 x.
+ * Per image a licv_resize_desc: source size h x w, resized size oh x ow, the crop (top, left, ch x cw) inside oh x ow, and its two plans
+ * inside `plans` (int32): a plan for out_size outputs with `ksize` taps is xmin[out_size], count[out_size], coef[out_size * ksize] from
+ * its offset (in elements); the horizontal plan is read when w != ow, the vertical when h != oh.  h == 0 or w == 0 is a missing image.
+ * The crop lands at the origin of the image's H x W frame; everything outside ch x cw is 0 (mask 0).  Output: either out_u8
+ * (n, H, W, 3) uint8, or out_bf16 (n, 3, H, W) = the table of licv_preprocess_images (rescale, mean3, std3: HOST pointers) applied to
+ * those bytes - bit-equal to licv_preprocess_images on the resized bytes; mask_u8 (n, H, W), optional, with either.
+ *
+ * desc_host is a HOST pointer (every check reads it), desc_dev a device copy of the same n records that is complete on `stream` before
+ * the call.  Checked before anything is launched (LICV_E_BADARG, nothing written): the crop inside oh x ow, ch <= H and cw <= W, the
+ * source rows inside src_bytes, the plans inside plan_elems, ws_offset as licv_resize_images_workspace set it.  A source row too
+ * long for the LDS staging (about 21 000 pixels) is LICV_E_UNSUPPORTED.  src and workspace 16-byte aligned.  Two launches: horizontal
+ * pass into the uint8 workspace (only the source rows and the output columns the crop needs), then vertical + crop + normalise.
+ * licv_resize_images_workspace WRITES desc_host[i].ws_offset (sum over the images with a horizontal pass of h * align16(3 cw)) and
+ * returns the total in *bytes; call it before uploading the descriptors. */
+typedef struct licv_resize_desc {
+    int64_t src_offset, src_ld_bytes, x0_bytes;
+    int64_t h, w, oh, ow;
+    int64_t top, left, ch, cw;
+    int64_t hplan_offset, hplan_ksize, vplan_offset, vplan_ksize;
+    int64_t ws_offset;
+} licv_resize_desc;
+int licv_resize_images_workspace(licv_resize_desc* desc_host, int64_t n_images, int64_t* bytes);
+int licv_resize_images(const void* src_u8, int64_t src_bytes, const licv_resize_desc* desc_host, const licv_resize_desc* desc_dev,
+                       int64_t n_images, const int32_t* plans, int64_t plan_elems, int64_t H, int64_t W, void* out_u8, void* out_bf16,
+                       void* mask_u8, double rescale, const float* mean3, const float* std3, void* workspace, int64_t workspace_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 // All of it is byte/integer work bounded by HBM bandwidth: coalesced 16-byte loads, one wave (or workgroup) per row / image.
 #include <cstring>
 #include "common.h"
+#include "image_table.h"
 
 // ------------------------------------------------------------------------------------------------
 // Idefics: token t of row b sees the most recent <image> before or at t (index = number of <image> tokens so far - 1),
@@ -207,10 +208,8 @@ extern "C" int licv_merge_image_rows(void* h_bf16, const int64_t* input_ids, con
 // zeros and marks real pixels).  A byte has 256 values: the 3 x 256 table of final bf16 values is computed on the HOST with exactly
 // those IEEE operations (so the result is the reference's float rounded once to bf16, bit for bit; the device's float division is
 // not the host's), handed to the kernel by value (1.5 KB of kernel arguments), copied to LDS, and the pixel loop is a table
-// look-up and a layout change: 3 bytes in, 3 bf16 planes out, consecutive lanes on consecutive pixels.
+// look-up and a layout change: 3 bytes in, 3 bf16 planes out, consecutive lanes on consecutive pixels.  (The table: image_table.h.)
 // ------------------------------------------------------------------------------------------------
-struct ImageTable { bf16_t v[3][256]; };
-
 __global__ __launch_bounds__(256)
 void image_preprocess_k(const unsigned char* __restrict__ src, const int32_t* __restrict__ hw, bf16_t* __restrict__ dst,
                         unsigned char* __restrict__ mask, int64_t n, int H, int W, ImageTable tb) {
@@ -240,16 +239,7 @@ extern "C" int licv_preprocess_images(const void* src_u8, const int32_t* valid_h
     LICV_CHECK_ARG(n_images >= 0 && H > 0 && W > 0 && H * W < (1ll << 31), "preprocess_images: bad shape");
     LICV_CHECK_ARG(std3[0] != 0.f && std3[1] != 0.f && std3[2] != 0.f, "preprocess_images: zero std");
     if (n_images == 0) return LICV_OK;
-    ImageTable tb;
-    for (int v = 0; v < 256; ++v) {
-        const volatile float x = (float)((double)v * rescale);        // hf:image_transforms.py:118-122 (volatile: one rounding per step,
-        for (int c = 0; c < 3; ++c) {                                 //  no wider intermediate, whatever the host compiler's flags)
-            const volatile float d = x - mean3[c];
-            const volatile float q = d / std3[c];                     // :437
-            uint32_t u; float qf = q; memcpy(&u, &qf, 4);
-            tb.v[c][v] = (bf16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);      // round to nearest even (finite values only)
-        }
-    }
+    const ImageTable tb = build_image_table(rescale, mean3, std3);
     int64_t bx = (H * W + 255) / 256; bx = bx > 64 ? 64 : bx;
     image_preprocess_k<<<dim3((unsigned)bx, (unsigned)n_images), 256, 0, (hipStream_t)stream>>>(
         (const unsigned char*)src_u8, valid_hw, (bf16_t*)dst_bf16, (unsigned char*)mask_u8, n_images, (int)H, (int)W, tb);

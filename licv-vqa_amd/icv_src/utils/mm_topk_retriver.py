@@ -25,18 +25,20 @@ def resize_center_crop_u8(img, size: int) -> np.ndarray:
     """hf CLIPImageProcessor up to its rescale step, on the host with PIL: RGB, shortest edge -> size (bicubic; the long edge is
     int(size * long / short)), centre crop size x size.  -> (size, size, 3) uint8."""
     from PIL import Image
+    from licv.frontend import clip_resize_geometry
     if not isinstance(img, Image.Image):
         img = Image.fromarray(np.asarray(img))
     img = img.convert("RGB")
     w, h = img.size
-    if w <= h:
-        nw, nh = size, int(size * h / w)
-    else:
-        nw, nh = int(size * w / h), size
+    (nw, nh), (left, top) = clip_resize_geometry(w, h, size)
     if (nw, nh) != (w, h):
         img = img.resize((nw, nh), resample=Image.BICUBIC)
-    left, top = (nw - size) // 2, (nh - size) // 2
     return np.asarray(img.crop((left, top, left + size, top + size)), dtype=np.uint8)
+
+
+def _to_pil(img):
+    from PIL import Image
+    return Image.fromarray(np.asarray(img))
 
 
 def resolve_clip_dir(name: str) -> Path:
@@ -53,6 +55,9 @@ def resolve_clip_dir(name: str) -> Path:
 
 
 class MMTopkRetriever:
+    device_resize = False      # True: resize + crop + normalise on the device (licv_resize_images, the bytes PIL would give) instead of
+                               # the PIL thread pool + licv_preprocess_images; only where no img_processor is given
+
     def __init__(self, index_ds: Sequence[dict], test_ds: Sequence[dict], clip_model_name: Optional[str] = "openai/clip-vit-base-patch32",
                  mode: Optional[str] = "i2t", index_field: Optional[str] = "text", test_field: Optional[str] = "image",
                  batch_size: Optional[int] = 1, num_workers: Optional[int] = 0, cache_file: Optional[str] = None, device: str = "cuda",
@@ -101,6 +106,14 @@ class MMTopkRetriever:
             return self._img_processor(images)
         from licv import frontend
         S = self.vision_encoder.arch.image_size
+        if self.device_resize:
+            rgb = [np.asarray((im if hasattr(im, "convert") else _to_pil(im)).convert("RGB")) for im in images]
+            sizes, crops = [], []
+            for a in rgb:
+                (nw, nh), (left, top) = frontend.clip_resize_geometry(a.shape[1], a.shape[0], S)
+                sizes.append((nh, nw))
+                crops.append((top, left, S, S))
+            return frontend.resize_images(rgb, sizes, crops, "bicubic", (S, S), normalize=(CLIP_MEAN, CLIP_STD), device=self.device)
         crop = lambda im: resize_center_crop_u8(im, S)
         u8 = np.stack(list(pool.map(crop, images)) if pool is not None else [crop(im) for im in images])
         return frontend.preprocess_images(torch.from_numpy(u8).to(self.device), mean=CLIP_MEAN, std=CLIP_STD)[0]

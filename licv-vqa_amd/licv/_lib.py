@@ -18,7 +18,7 @@ LAB_PATH = Path(os.environ.get("LICV_HIP_LAB_LIB", _HERE / "liblicv_hip_lab.so")
 LAB_HEADER = _HERE.parents[1] / "include" / "licv_hip_lab.h"
 
 LICV_BF16, LICV_F32 = 0, 1
-ABI_VERSION = 8          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
+ABI_VERSION = 9          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
 
 _lib = None
 _lab = None
@@ -168,6 +168,8 @@ def lib() -> C.CDLL:
             "licv_topk_ip": [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, P],
             "licv_l2_normalize_rows": [P, I, P, I64, I64, P],
             "licv_quick_gelu": [P, I64, I64, I64, P],
+            "licv_resize_images_workspace": [P, I64, P],
+            "licv_resize_images": [P, I64, P, P, I64, P, I64, I64, I64, P, P, P, C.c_double, P, P, P, I64, P],
         }
         for name, args in sig.items():
             fn = getattr(_lib, name)

@@ -10,6 +10,10 @@ normalised bf16 pixel_values on the device (licv.frontend.preprocess_images, one
     ...                                                        # the step before this one is still computing on the main stream
     pixel_values, mask = feeder.get(t, B, N)                   # the main stream waits for THAT batch's event only
 
+With `resize="bicubic"` / `"bilinear"` the feeder takes RAW images of any size: their bytes are packed into pinned memory as they are
+and the resize runs on the side stream too (licv.frontend.resize_images' kernels, bit-equal to PIL's Image.resize), to the frame
+H x W (the Idefics v1 rule, resize((224, 224), BICUBIC)) or to a per-image (out_h, out_w) inside the padded frame with mask (Idefics2).
+
 `submit` returns at once (the copy and the kernel are queued on the side stream); a staging buffer is reused only after the event
 of the batch that last used it has completed.  32-shot at ~43 questions/s is ~1.4 k images/s per GPU (~210 MB/s of bytes): the
 link is nowhere near busy, what matters is that nothing of it sits on the step's critical path.
@@ -26,16 +30,22 @@ from . import frontend
 
 class ImageFeeder:
     def __init__(self, device, max_images: int, height: int, width: int, mean=frontend.IDEFICS_MEAN, std=frontend.IDEFICS_STD,
-                 rescale: float = 1 / 255, with_mask: bool = False, depth: int = 2):
+                 rescale: float = 1 / 255, with_mask: bool = False, depth: int = 2, resize: Optional[str] = None,
+                 max_src_bytes: Optional[int] = None):
         self.device = torch.device(device)
         self.max_images, self.H, self.W = int(max_images), int(height), int(width)
         self.mean, self.std, self.rescale, self.with_mask = tuple(mean), tuple(std), float(rescale), bool(with_mask)
         self.depth = int(depth)
         shape = (self.max_images, self.H, self.W, 3)
-        self.host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
-        self.host_hw = [torch.empty((self.max_images, 2), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
-        self.dev_u8 = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
-        self.dev_hw = [torch.empty((self.max_images, 2), dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+        self.resize = None if resize is None else frontend._filter_name(resize)
+        if self.resize is None:
+            self.host = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+            self.host_hw = [torch.empty((self.max_images, 2), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+            self.dev_u8 = [torch.empty(shape, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
+            self.dev_hw = [torch.empty((self.max_images, 2), dtype=torch.int32, device=self.device) for _ in range(self.depth)]
+        else:                                               # raw images of any size: packed bytes + descriptors + plans per slot
+            nbytes = int(max_src_bytes) if max_src_bytes is not None else 4 * self.max_images * self.H * self.W * 3
+            self.stages = [frontend.ResizeStage(self.device, nbytes, self.max_images, fixed=True) for _ in range(self.depth)]
         self.out = [torch.empty((self.max_images, 3, self.H, self.W), dtype=torch.bfloat16, device=self.device) for _ in range(self.depth)]
         self.mask = [torch.empty((self.max_images, self.H, self.W), dtype=torch.uint8, device=self.device) if with_mask else None
                      for _ in range(self.depth)]
@@ -76,13 +86,20 @@ class ImageFeeder:
             hw[i, 0] = h; hw[i, 1] = w
         return n, ragged
 
-    def submit(self, images) -> Tuple[int, int]:
-        """Queue one batch; returns a ticket for get()."""
+    def submit(self, images, sizes: Optional[Sequence] = None) -> Tuple[int, int]:
+        """Queue one batch; returns a ticket for get().  With `resize`: images are raw (h, w, 3) uint8 arrays / PIL images / None of
+        any size, `sizes` optionally one (out_h, out_w) <= (H, W) per image (default: the frame H x W)."""
         slot = self.turn
         self.turn = (self.turn + 1) % self.depth
         if self.done[slot] is not None:
             self.done[slot].synchronize()                   # the H2D copy out of this pinned buffer has finished
-        n, ragged = self._pack(slot, images)
+        if self.resize is not None:
+            n = len(images)
+            assert n <= self.max_images and (sizes is None or len(sizes) == n)
+            self.stages[slot].pack(images, sizes if sizes is not None else [(self.H, self.W)] * n, None, self.resize)
+        else:
+            assert sizes is None, "ImageFeeder: per-image sizes need resize="
+            n, ragged = self._pack(slot, images)
         if self.handed_out[slot]:
             # The slot's output was handed out by get() and never release()d: the forward that reads it was issued on the caller's
             # stream some time between that get() and now, so an event recorded on that stream NOW is behind it.  (release() marks the
@@ -94,15 +111,19 @@ class ImageFeeder:
         with torch.cuda.stream(self.stream):
             if self.consumed[slot] is not None:
                 self.stream.wait_event(self.consumed[slot])  # the step that read this slot's output has finished with it
-            self.dev_u8[slot][:n].copy_(self.host[slot][:n], non_blocking=True)
-            hw = None
-            if ragged or self.with_mask:
-                if not ragged:
-                    self.host_hw[slot][:n, 0] = self.H; self.host_hw[slot][:n, 1] = self.W
-                self.dev_hw[slot][:n].copy_(self.host_hw[slot][:n], non_blocking=True)
-                hw = self.dev_hw[slot][:n]
-            frontend.preprocess_images(self.dev_u8[slot][:n], self.mean, self.std, self.rescale, valid_hw=hw,
-                                       out=self.out[slot][:n], mask_out=self.mask[slot][:n] if self.with_mask else None)
+            if self.resize is not None:
+                self.stages[slot].launch(self.H, self.W, out_bf16=self.out[slot][:n], mask=self.mask[slot][:n] if self.with_mask else None,
+                                         mean=self.mean, std=self.std, rescale=self.rescale)
+            else:
+                self.dev_u8[slot][:n].copy_(self.host[slot][:n], non_blocking=True)
+                hw = None
+                if ragged or self.with_mask:
+                    if not ragged:
+                        self.host_hw[slot][:n, 0] = self.H; self.host_hw[slot][:n, 1] = self.W
+                    self.dev_hw[slot][:n].copy_(self.host_hw[slot][:n], non_blocking=True)
+                    hw = self.dev_hw[slot][:n]
+                frontend.preprocess_images(self.dev_u8[slot][:n], self.mean, self.std, self.rescale, valid_hw=hw,
+                                           out=self.out[slot][:n], mask_out=self.mask[slot][:n] if self.with_mask else None)
             ev = torch.cuda.Event()
             ev.record(self.stream)
         self.done[slot] = ev

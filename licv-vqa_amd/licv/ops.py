@@ -700,3 +700,10 @@ def quick_gelu_(x: torch.Tensor, rows: Optional[int] = None, dim: Optional[int] 
 
 
 quick_gelu = quick_gelu_
+
+
+# ------------------------------------------------------------------------------------------ image resize (bit-equal to Pillow)
+def resize_images(*args, **kwargs):
+    """licv.frontend.resize_images (the resize lives with the image front-end; this name completes the op list)."""
+    from . import frontend
+    return frontend.resize_images(*args, **kwargs)
