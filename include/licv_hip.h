@@ -24,7 +24,9 @@ extern "C" {
  * library that answers anything else.  1 = round 1; 2 = rounds 2-3 (fp8, split-K slices, runner, front-end, backward, image input);
  * 3-6 = round 4 (lab library split off; weight-streaming GEMM; beam scoring; decode-step fusion; backward options; RMSNorm backward
  * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step); 8 = RICE retrieval
- * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu); 9 = image resize on the device (licv_resize_images). */
+ * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu); 9 = image resize on the device (licv_resize_images); still 9 with
+ * the CLIP text tower's kernels (licv_clip_text_embed, licv_attn_varlen_causal, licv_layernorm_rows_fwd): they only ADD symbols - no
+ * existing entry point changed, so a binding written against 9 keeps working (check_exports still asks for every declared symbol). */
 #define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
@@ -546,6 +548,38 @@ int licv_resize_images(const void* src_u8, int64_t src_bytes, const licv_resize_
                        int64_t n_images, const int32_t* plans, int64_t plan_elems, int64_t H, int64_t W, void* out_u8, void* out_bf16,
                        void* mask_u8, double rescale, const float* mean3, const float* std3, void* workspace, int64_t workspace_bytes,
                        void* stream);
+
+/* ---- CLIP text tower on PACKED tokens (ref:icv_src/utils/mm_topk_retriver.py encode_text -> hf CLIPTextModelWithProjection).  The
+ * tower is causal (hf:clip/modeling_clip.py:543-556, create_causal_mask + is_causal=True), so the state of a token never depends on
+ * what follows it: the valid tokens of a right-padded batch, laid back to back (`total` rows, sequence i = rows cu_seqlens[i] ..
+ * cu_seqlens[i + 1] - 1), give the padded tower's states exactly, and the GEMMs and the attention do no work on padding. ---- */
+/* hf:clip/modeling_clip.py:221-256 (CLIPTextEmbeddings.forward: token_embedding(input_ids) + position_embedding(position_ids)) on
+ * packed ids: out[t, :] = bf16(tok[ids[t], :] + pos[positions[t], :]), the sum in fp32 and rounded once (torch's bf16 add).  ids
+ * (total) int64 and positions (total) int32 are DEVICE arrays; the position of a token inside its sequence is made on the host together
+ * with cu_seqlens (licv.clip_engine.pack_text_batch), which also validates 0 <= id < vocab and 0 <= position < n_pos before the launch.
+ * The kernel reads neither table outside its rows: an id or a position out of range writes a row of zeros.  dim % 8 == 0; tables and
+ * out 16-byte aligned; out (total, dim) dense. */
+int licv_clip_text_embed(const int64_t* ids, const int32_t* positions, const void* tok_bf16, const void* pos_bf16, void* out_bf16,
+                         int64_t total, int64_t dim, int64_t vocab, int64_t n_pos, void* stream);
+/* hf:clip/modeling_clip.py:259-277 (eager_attention_forward) + :280-335 (CLIPAttention.forward) under the causal mask of :543-548, over
+ * a packed (total, ld_qkv) bf16 buffer of fused projections [Q | K | V], each n_heads * head_dim wide: token i of a sequence attends
+ * to tokens 0 .. i of the SAME sequence and to nothing else.  out (total, n_heads * head_dim) bf16 dense; rows past `total` are not
+ * touched.  cu_seqlens: n_seq + 1 int32, [0] = 0, ascending; given twice - cu_seqlens_host (HOST pointer, every check reads it) and
+ * cu_seqlens_dev (a device copy, complete on `stream` before the call; a copy that disagrees with the host's cannot take the kernel
+ * out of the buffers - such sequences are skipped).  head_dim must be 64 and every length 1 .. 128: the whole K and V of one
+ * (sequence, head) stay in LDS, the softmax is one fp32 pass over the resident scores, key tiles above the diagonal are skipped.
+ * Rounding points as licv_attn_fwd (exp2 of fp32 scores, bf16 probabilities into the PV MFMA, fp32 accumulators, bf16 output).  A row's
+ * result depends on its own sequence only: the same bits alone or in any batch.  head_dim != 64, a length of 0 or above 128,
+ * cu_seqlens not ascending from 0, ld_qkv < 3 * n_heads * head_dim or not a multiple of 8, scale <= 0, misaligned pointers:
+ * LICV_E_BADARG, nothing launched. */
+int licv_attn_varlen_causal(const void* qkv_bf16, int64_t ld_qkv, const int32_t* cu_seqlens_host, const int32_t* cu_seqlens_dev,
+                            int64_t n_seq, int64_t n_heads, int64_t head_dim, float scale, void* out_bf16, void* stream);
+/* hf:clip/modeling_clip.py:558-581 (final_layer_norm, then the pooled row of every sequence) with the order swapped, which LayerNorm
+ * being row-wise allows: out[j, :] = LayerNorm(x[rows[j], :]) for n_rows selected rows of a (n_src_rows, ld_x) bf16 buffer, fp32
+ * statistics and one rounding as licv_layernorm_fwd.  rows: DEVICE int32; an index outside [0, n_src_rows) reads nothing and writes a
+ * row of zeros.  out (n_rows, dim) dense. */
+int licv_layernorm_rows_fwd(const void* x_bf16, int64_t ld_x, int64_t n_src_rows, const int32_t* rows, const void* w_bf16,
+                            const void* b_bf16, void* out_bf16, int64_t n_rows, int64_t dim, float eps, void* stream);
 
 #ifdef __cplusplus
 }

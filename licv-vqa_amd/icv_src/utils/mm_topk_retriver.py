@@ -1,16 +1,21 @@
-"""RICE retrieval (retrieval by image similarity) behind the reference's interface: `MMTopkRetriever` of
+"""Retrieval of in-context examples by CLIP similarity behind the reference's interface: `MMTopkRetriever` of
 ref:icv_src/utils/mm_topk_retriver.py (the reference's spelling of the file name), as ref:inference.py:185-199 constructs it and
-:204 calls it.  Same constructor surface, attributes and cache-file layout; underneath, the CLIP image tower runs on the native
-engine (licv/clip_engine.py) and the exact inner-product search that the reference hands to faiss.IndexFlatIP is one fused HIP kernel
-(licv_topk_ip).  Equal scores resolve to the lowest index (faiss leaves ties unspecified).
+:204 calls it.  Same constructor surface, attributes and cache-file layout; underneath, both CLIP towers run on the native engines
+(licv/clip_engine.py: the image tower, and the text tower on packed tokens) and the exact inner-product search that the reference hands
+to faiss.IndexFlatIP is one fused HIP kernel (licv_topk_ip).  Equal scores resolve to the lowest index (faiss leaves ties unspecified).
+All four modes compute: "i2i", "t2t", and the mixed "i2t" / "t2i" (test side first, as the reference reads the mode string).
 
-What differs, on purpose: there is no network, so `clip_model_name` has to resolve to a local directory; the text tower and the
-tokenizer are out of scope, so a mode with a "t" in it works from a cache file only; `cache_file=None` computes without saving."""
+What differs, on purpose: there is no network, so `clip_model_name` has to resolve to a local directory unless the towers are handed
+over in `clip_weights`; the tokenizer is not ours - it is the one `transformers.AutoTokenizer.from_pretrained(<that directory>,
+local_files_only=True)` gives, or any callable given in `clip_weights`; only the towers a mode needs are built; a text mode without a
+text tower (none given, no local checkpoint) raises NotImplementedError before anything else happens; `cache_file=None` computes
+without saving."""
 from __future__ import annotations
 
 import os
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from collections.abc import Mapping
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -62,9 +67,11 @@ class MMTopkRetriever:
                  mode: Optional[str] = "i2t", index_field: Optional[str] = "text", test_field: Optional[str] = "image",
                  batch_size: Optional[int] = 1, num_workers: Optional[int] = 0, cache_file: Optional[str] = None, device: str = "cuda",
                  reversed_order: Optional[bool] = False, *, clip_weights=None, img_processor: Optional[Callable] = None) -> None:
-        """As the reference class.  Keyword-only extras: `clip_weights` = (ClipVisionArch, state dict) of a tower held in memory
-        (then clip_model_name is a label only); `img_processor` = callable, list of images -> (n, 3, S, S) tensor, replacing the
-        built-in CLIPImageProcessor restatement."""
+        """As the reference class.  Keyword-only extras: `clip_weights` = (ClipVisionArch, state dict) of an image tower held in memory,
+        or a mapping with any of "vision": (ClipVisionArch, state dict), "text": (ClipTextArch, state dict), "tokenizer": a callable used as
+        tok(texts, padding=True, return_tensors="pt", truncation=True) -> input_ids / attention_mask (what is not given comes from the
+        local directory clip_model_name resolves to); `img_processor` = callable, list of images -> (n, 3, S, S) tensor, replacing
+        the built-in CLIPImageProcessor restatement."""
         self.index_ds, self.test_ds = index_ds, test_ds
         self.clip_model_name = clip_model_name
         self.device = device
@@ -83,23 +90,71 @@ class MMTopkRetriever:
             self.test_features = np.ascontiguousarray(features["test_features"], dtype=np.float32)
 
     # ------------------------------------------------------------------------------------------ features
+    def _given(self, what: str):
+        """The entry `what` ("vision", "text", "tokenizer") of clip_weights, or None; the 2-tuple form is the image tower."""
+        cw = self._clip_weights
+        if isinstance(cw, Mapping):
+            return cw.get(what)
+        return cw if what == "vision" else None
+
     def create_index(self, cache_file: Optional[str]) -> None:
         index_enc, test_enc = self.mode.split("2")[1], self.mode.split("2")[0]
-        if "t" in (index_enc, test_enc):
-            raise NotImplementedError(f"mode {self.mode!r} needs the CLIP text tower, which this package does not have: compute 'i2i' "
-                                      f"features, or pass a cache_file written by the reference")
-        from licv.clip_engine import ClipVisionEngine, load_clip_vision
-        arch, sd = self._clip_weights if self._clip_weights is not None else load_clip_vision(resolve_clip_dir(self.clip_model_name))
-        self.vision_encoder = ClipVisionEngine(arch, sd, self.device)
-        index_dev = self.encode_img(self.index_ds, self.index_field)
-        test_dev = self.encode_img(self.test_ds, self.test_field)
+        need = {index_enc, test_enc}
+        clip_dir = None
+        if "t" in need and self._given("text") is None:
+            try:
+                clip_dir = resolve_clip_dir(self.clip_model_name)
+            except (FileNotFoundError, TypeError) as e:
+                raise NotImplementedError(f"mode {self.mode!r} needs the CLIP text tower: none was given in clip_weights and no local checkpoint "
+                                          f"was found for {self.clip_model_name!r} ({e}); compute 'i2i' features, pass the tower, or pass a "
+                                          f"cache_file written by the reference") from None
+        from licv import clip_engine as CE
+        local = lambda: clip_dir if clip_dir is not None else resolve_clip_dir(self.clip_model_name)
+        towers = {}
+        if "i" in need:
+            towers["i"] = self._given("vision") or CE.load_clip_vision(local())
+        if "t" in need:
+            towers["t"] = self._given("text") or CE.load_clip_text(local())
+        if len(towers) == 2 and towers["i"][0].projection_dim != towers["t"][0].projection_dim:
+            raise ValueError(f"mode {self.mode!r} compares image and text features, but the towers project to {towers['i'][0].projection_dim} "
+                             f"and {towers['t'][0].projection_dim} dimensions")
+        if "t" in need:
+            self.tokenizer = self._given("tokenizer")
+            if self.tokenizer is None:
+                from transformers import AutoTokenizer
+                self.tokenizer = AutoTokenizer.from_pretrained(str(local()), local_files_only=True)
+            self.text_encoder = CE.ClipTextEngine(*towers["t"], self.device)
+        if "i" in need:
+            self.vision_encoder = CE.ClipVisionEngine(*towers["i"], self.device)
+        encode = {"i": self.encode_img, "t": self.encode_text}
+        index_dev = encode[index_enc](self.index_ds, self.index_field)
+        test_dev = encode[test_enc](self.test_ds, self.test_field)
         self._index_dev, self._test_dev = index_dev, test_dev
         self.index_features, self.test_features = index_dev.cpu().numpy(), test_dev.cpu().numpy()
         if cache_file is not None:
             torch.save({"index_features": self.index_features, "test_features": self.test_features,
                         "meta_info": {"clip_model_name": self.clip_model_name, "mode": self.mode, "index_field": self.index_field,
                                       "test_field": self.test_field}}, cache_file)
-        del self.vision_encoder
+        for name in ("vision_encoder", "text_encoder"):
+            if hasattr(self, name):
+                delattr(self, name)
+
+    @torch.inference_mode()
+    def encode_text(self, ds: Sequence[dict], text_field: str) -> torch.Tensor:
+        """Every text of `ds` through the tokenizer and the tower, `batch_size` at a time: each batch is tokenized as the reference does
+        (padded to its longest member), packed to its valid tokens and run in one pass -> (len(ds), dim) fp32 unit rows on the device."""
+        n = len(ds)
+        out = None
+        for b0 in range(0, n, self.batch_size):
+            texts = [ds[i][text_field] for i in range(b0, min(n, b0 + self.batch_size))]
+            enc = self.tokenizer(texts, padding=True, return_tensors="pt", truncation=True)
+            feats = self.text_encoder.encode(enc["input_ids"], enc["attention_mask"])
+            if out is None:
+                out = torch.empty((n, feats.shape[1]), dtype=torch.float32, device=feats.device)
+            out[b0:b0 + len(texts)] = feats
+        if out is None:
+            raise ValueError("encode_text: empty dataset")
+        return out
 
     def _pixel_values(self, images: list, pool) -> torch.Tensor:
         if self._img_processor is not None:

@@ -170,6 +170,9 @@ def lib() -> C.CDLL:
             "licv_quick_gelu": [P, I64, I64, I64, P],
             "licv_resize_images_workspace": [P, I64, P],
             "licv_resize_images": [P, I64, P, P, I64, P, I64, I64, I64, P, P, P, C.c_double, P, P, P, I64, P],
+            "licv_clip_text_embed": [P, P, P, P, P, I64, I64, I64, I64, P],
+            "licv_attn_varlen_causal": [P, I64, P, P, I64, I64, I64, F, P, P],
+            "licv_layernorm_rows_fwd": [P, I64, I64, P, P, P, P, I64, I64, F, P],
         }
         for name, args in sig.items():
             fn = getattr(_lib, name)

@@ -1,19 +1,25 @@
-"""The CLIP image tower with projection (hf:clip/modeling_clip.py CLIPVisionModelWithProjection) on the library's kernels: what the
-reference's retriever encodes every index and test image with (ref:icv_src/utils/mm_topk_retriver.py, mode "i2i").
+"""The CLIP towers with projection (hf:clip/modeling_clip.py CLIPVisionModelWithProjection, CLIPTextModelWithProjection) on the
+library's kernels: what the reference's retriever encodes every index and test image / text with
+(ref:icv_src/utils/mm_topk_retriver.py encode_img, encode_text).
 
 bf16 weights and activations like both LMM engines; the features leave as fp32 unit rows (what the reference hands to faiss).  The
 tower is the Idefics vision tower's architecture family and runs on the same ops (im2col + GEMM patch embedding, fused cls + position +
 pre_layrnorm, LayerNorm, unmasked attention, GEMMs with bias / residual epilogues); new are QuickGELU, the class-token pick (a strided
-LayerNorm: row 0 of every T) and the row normalisation."""
+LayerNorm: row 0 of every T) and the row normalisation.
+
+The text tower is causal, so it runs on the VALID tokens only, packed back to back (pack_text_batch): the token + position embedding on
+packed ids, causal attention over the ragged batch (licv_attn_varlen_causal), the same GEMMs on `total` rows instead of n x S, and the
+final LayerNorm on the end-of-text rows only.  That is exact, not an approximation: a right-padded row and the same row alone give the
+same text_embeds in transformers.  There is no padded second path; ClipTextArch refuses what the packed kernels cannot serve."""
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import ops
-from .config import ClipVisionArch
+from .config import ClipTextArch, ClipVisionArch
 from .idefics_engine import _bf, _pad_cols, _VitLayer
 
 
@@ -101,3 +107,131 @@ class ClipVisionEngine:
     def encode(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """pixel_values (n, 3, S, S) -> (n, projection_dim) fp32 unit rows on the device."""
         return ops.l2_normalize_rows(self.image_embeds(pixel_values).contiguous())
+
+
+# ------------------------------------------------------------------------------------------------ text tower
+def clip_text_state(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The tower's tensors under the key names of CLIPTextModelWithProjection (`text_model.*`, `text_projection.weight`): also the names
+    inside a full CLIPModel checkpoint, whose vision tower and `logit_scale` are dropped."""
+    out = {k: v for k, v in sd.items() if k.startswith("text_model.") or k == "text_projection.weight"}
+    if "text_projection.weight" not in out or "text_model.embeddings.token_embedding.weight" not in out:
+        raise KeyError("state dict holds no CLIP text tower (text_model.*, text_projection.weight)")
+    return out
+
+
+def load_clip_text(path) -> Tuple[ClipTextArch, Dict[str, torch.Tensor]]:
+    """(arch, state dict) from a local directory with config.json + *.safetensors shards."""
+    from .checkpoint import read_config_json, read_safetensors_dir
+    path = Path(path)
+    sd = read_safetensors_dir(path)
+    return ClipTextArch.from_hf(read_config_json(path)), clip_text_state(sd)
+
+
+class PackedText(NamedTuple):
+    ids: torch.Tensor            # (total,) int64: the valid tokens of every row, back to back
+    cu_seqlens: torch.Tensor     # (n + 1,) int32: row i = packed rows cu_seqlens[i] .. cu_seqlens[i + 1] - 1
+    pool_rows: torch.Tensor      # (n,) int32: the PACKED row whose state is row i's pooled output
+    positions: torch.Tensor      # (total,) int32: position of every packed token inside its row
+
+
+def pack_text_batch(input_ids, attention_mask, arch: ClipTextArch) -> PackedText:
+    """A right-padded tokenizer batch (input_ids, attention_mask: (n, S)) -> its valid tokens packed, all on the host.
+    The pooled position follows hf:clip/modeling_clip.py:561-581 on the PADDED ids: with config eos_token_id == 2 the first position of
+    the row's largest id, otherwise the first position of eos_token_id (position 0 when the row holds none, as argmax gives).
+    ValueError: a mask that is not a non-empty prefix of ones, a length above max_position_embeddings, an id outside the vocabulary,
+    a pooled position that falls into the padding (the padded tower would pool a padding state there)."""
+    ids = torch.as_tensor(input_ids).cpu()
+    if ids.dim() != 2 or ids.dtype not in (torch.int64, torch.int32, torch.int16, torch.uint8):
+        raise ValueError(f"input_ids: an (n, S) integer tensor is expected, got {tuple(ids.shape)} {ids.dtype}")
+    ids = ids.to(torch.int64)
+    n, S = ids.shape
+    mask = torch.ones((n, S), dtype=torch.int64) if attention_mask is None else torch.as_tensor(attention_mask).cpu().to(torch.int64)
+    if mask.shape != ids.shape or n == 0 or S == 0:
+        raise ValueError(f"attention_mask {tuple(mask.shape)} does not match input_ids {tuple(ids.shape)} (a non-empty batch is expected)")
+    lens = mask.sum(1)
+    valid = torch.arange(S)[None, :] < lens[:, None]
+    if not torch.equal(mask != 0, valid) or not ((mask == 0) | (mask == 1)).all():
+        bad = int(((mask != 0) != valid).any(1).nonzero()[0]) if not torch.equal(mask != 0, valid) else 0
+        raise ValueError(f"attention_mask row {bad} is not a prefix of ones: only right-padded batches can be packed")
+    if int(lens.min()) < 1:
+        raise ValueError(f"attention_mask row {int(lens.argmin())} is empty")
+    if int(lens.max()) > arch.max_position_embeddings:
+        raise ValueError(f"row {int(lens.argmax())} holds {int(lens.max())} tokens, the tower has {arch.max_position_embeddings} positions "
+                         f"(tokenize with truncation=True)")
+    packed = ids[valid]
+    if int(packed.min()) < 0 or int(packed.max()) >= arch.vocab_size:
+        raise ValueError(f"token id {int(packed.max()) if int(packed.max()) >= arch.vocab_size else int(packed.min())} is outside the "
+                         f"vocabulary [0, {arch.vocab_size})")
+    pool = ids.argmax(dim=-1) if arch.eos_token_id == 2 else (ids == arch.eos_token_id).to(torch.int64).argmax(dim=-1)
+    if (pool >= lens).any():
+        bad = int((pool >= lens).nonzero()[0])
+        raise ValueError(f"row {bad}: the pooled position {int(pool[bad])} (eos_token_id {arch.eos_token_id}) falls into the padding "
+                         f"(the row holds {int(lens[bad])} tokens)")
+    cu = torch.zeros(n + 1, dtype=torch.int64)
+    cu[1:] = lens.cumsum(0)
+    positions = (torch.arange(S)[None, :].expand(n, S))[valid]
+    return PackedText(packed.contiguous(), cu.to(torch.int32), (cu[:-1] + pool).to(torch.int32), positions.to(torch.int32).contiguous())
+
+
+class ClipTextEngine:
+    def __init__(self, arch: ClipTextArch, state_dict: Dict[str, torch.Tensor], device="cuda"):
+        a, dev = arch, torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ClipTextEngine runs on the GPU only (liblicv_hip has no CPU fallback)")
+        sd = clip_text_state(state_dict)
+        self.arch, self.device = a, dev
+        g = lambda k: _bf(sd[k], dev)
+        tp = "text_model."
+        self.tok = g(tp + "embeddings.token_embedding.weight")
+        self.pos = g(tp + "embeddings.position_embedding.weight")
+        assert self.tok.shape == (a.vocab_size, a.hidden_size), f"token table {tuple(self.tok.shape)} does not match the config"
+        assert self.pos.shape == (a.max_position_embeddings, a.hidden_size), f"position table {tuple(self.pos.shape)} does not match the config"
+        self.layers = []
+        for i in range(a.num_hidden_layers):
+            p = f"{tp}encoder.layers.{i}."
+            cat = lambda suf: torch.cat([g(p + f"self_attn.{n}_proj.{suf}") for n in ("q", "k", "v")]).contiguous()
+            self.layers.append(_VitLayer(g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias"), cat("weight"), cat("bias"),
+                                         g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"),
+                                         g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias"),
+                                         g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")))
+        self.final_ln_w, self.final_ln_b = g(tp + "final_layer_norm.weight"), g(tp + "final_layer_norm.bias")
+        self.proj_w = g("text_projection.weight")
+        assert self.proj_w.shape == (a.projection_dim, a.hidden_size)
+
+    @torch.no_grad()
+    def text_embeds(self, input_ids, attention_mask=None, hidden_states: Optional[list] = None) -> torch.Tensor:
+        """input_ids, attention_mask (n, S), right-padded -> the un-normalised text_embeds (n, projection_dim) bf16; one pass over the
+        batch's valid tokens.  `hidden_states`: a list that receives the PACKED (total, hidden) states HF's output_hidden_states holds at
+        the valid positions (the embedding output and every layer's), for tests."""
+        a = self.arch
+        pk = pack_text_batch(input_ids, attention_mask, a)
+        E, nh, hd = a.hidden_size, a.num_attention_heads, a.head_dim
+        cu_dev, rows_dev = pk.cu_seqlens.to(self.device), pk.pool_rows.to(self.device)
+        x = ops.clip_text_embed(pk.ids.to(self.device), pk.positions.to(self.device), self.tok, self.pos)
+        total = x.shape[0]
+        if hidden_states is not None:
+            hidden_states.append(x.clone())
+        for L in self.layers:
+            y = ops.layernorm(x, L.ln1_w, L.ln1_b, a.layer_norm_eps)
+            qkv = ops.linear(y, L.qkv_w, bias=L.qkv_b)
+            o = ops.attn_varlen_causal(qkv, pk.cu_seqlens, cu_dev, nh, hd, hd ** -0.5)
+            del qkv
+            ops.linear(o, L.out_w, bias=L.out_b, residual=x, out=x)
+            y = ops.layernorm(x, L.ln2_w, L.ln2_b, a.layer_norm_eps)
+            if a.hidden_act == "quick_gelu":
+                y = ops.quick_gelu_(ops.linear(y, L.fc1_w, bias=L.fc1_b))
+            else:
+                y = ops.linear(y, L.fc1_w, bias=L.fc1_b, act="gelu")
+            ops.linear(y, L.fc2_w, bias=L.fc2_b, residual=x, out=x)
+            del y, o
+            if hidden_states is not None:
+                hidden_states.append(x.clone())
+        assert x.shape == (total, E)
+        # pooled = final_layer_norm(last_hidden_state)[row, eos position]: the norm is row-wise, so only the pooled rows go through it
+        pooled = ops.layernorm_rows(x, rows_dev, self.final_ln_w, self.final_ln_b, a.layer_norm_eps)
+        return ops.linear(pooled, self.proj_w)
+
+    @torch.no_grad()
+    def encode(self, input_ids, attention_mask=None) -> torch.Tensor:
+        """input_ids, attention_mask (n, S) -> (n, projection_dim) fp32 unit rows on the device."""
+        return ops.l2_normalize_rows(self.text_embeds(input_ids, attention_mask).contiguous())

@@ -256,3 +256,71 @@ class ClipVisionArch:
 
 
 CLIP_VIT_B32 = ClipVisionArch()           # the public openai/clip-vit-base-patch32 numbers: bench / full-width tests without a checkpoint
+
+
+# ------------------------------------------------------------------------------------------ CLIP text tower (text modes of retrieval)
+CLIP_TEXT_HEAD_DIM = 64                   # licv_attn_varlen_causal: the head dimension of every public CLIP text tower
+CLIP_TEXT_MAX_POSITIONS = 128             # ... and its longest sequence (K and V of one (sequence, head) stay in LDS)
+
+
+@dataclass(frozen=True)
+class ClipTextArch:
+    """hf:clip/configuration_clip.py CLIPTextConfig: the text tower the reference's retriever encodes questions with
+    (ref:icv_src/utils/mm_topk_retriver.py encode_text).  The tower runs on packed tokens through licv_attn_varlen_causal only, so a
+    config that kernel cannot serve is refused here - there is no second path."""
+    vocab_size: int = 49408
+    hidden_size: int = 512
+    intermediate_size: int = 2048
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 8
+    max_position_embeddings: int = 77
+    projection_dim: int = 512
+    layer_norm_eps: float = 1e-5
+    hidden_act: str = "quick_gelu"
+    eos_token_id: int = 2
+
+    def __post_init__(self):
+        if self.hidden_act not in CLIP_HIDDEN_ACTS:
+            raise ValueError(f"CLIP hidden_act {self.hidden_act!r} is not supported (one of {CLIP_HIDDEN_ACTS})")
+        if self.hidden_size % self.num_attention_heads:
+            raise ValueError("CLIP text config: hidden_size % num_attention_heads must be 0")
+        if self.head_dim != CLIP_TEXT_HEAD_DIM:
+            raise ValueError(f"CLIP text config: head_dim {self.head_dim} is not supported (the packed attention kernel serves head_dim "
+                             f"{CLIP_TEXT_HEAD_DIM} only)")
+        if not 1 <= self.max_position_embeddings <= CLIP_TEXT_MAX_POSITIONS:
+            raise ValueError(f"CLIP text config: max_position_embeddings {self.max_position_embeddings} is not supported (at most "
+                             f"{CLIP_TEXT_MAX_POSITIONS})")
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden_size // self.num_attention_heads
+
+    def to_dict(self):
+        return asdict(self)
+
+    @staticmethod
+    def from_hf(cfg) -> "ClipTextArch":
+        """From a transformers CLIPTextConfig / CLIPConfig, or the dict of a config.json (a full CLIPModel's config keeps the tower under
+        `text_config` and projection_dim at the top level)."""
+        get = (lambda o, k, d=None: o.get(k, d)) if isinstance(cfg, dict) else (lambda o, k, d=None: getattr(o, k, d))
+        txt = get(cfg, "text_config")
+        proj = get(cfg, "projection_dim")
+        if txt is not None:
+            get_t = (lambda k, d=None: txt.get(k, d)) if isinstance(txt, dict) else (lambda k, d=None: getattr(txt, k, d))
+        else:
+            get_t = lambda k, d=None: get(cfg, k, d)
+        kw = {}
+        for f in ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings",
+                  "layer_norm_eps", "hidden_act", "eos_token_id"):
+            v = get_t(f)
+            if v is None:
+                raise KeyError(f"CLIP text config lacks {f!r}")
+            kw[f] = v
+        if proj is None:
+            proj = get_t("projection_dim")
+        if proj is None:
+            raise KeyError("CLIP config lacks 'projection_dim'")
+        return ClipTextArch(projection_dim=int(proj), **kw)
+
+
+CLIP_TEXT_B32 = ClipTextArch()            # the public openai/clip-vit-base-patch32 text numbers

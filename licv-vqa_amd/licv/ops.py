@@ -702,6 +702,53 @@ def quick_gelu_(x: torch.Tensor, rows: Optional[int] = None, dim: Optional[int] 
 quick_gelu = quick_gelu_
 
 
+# ------------------------------------------------------------------------------------------ CLIP text tower on packed tokens
+def clip_text_embed(ids: torch.Tensor, positions: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """out[t] = bf16(tok[ids[t]] + pos[positions[t]]): ids (total,) int64, positions (total,) int32, tables bf16 -> (total, dim) bf16.
+    The caller has validated ids and positions on the host (pack_text_batch); out-of-range entries come back as zero rows."""
+    assert ids.dtype == torch.int64 and positions.dtype == torch.int32 and ids.is_contiguous() and positions.is_contiguous()
+    assert ids.dim() == 1 and ids.shape == positions.shape and ids.is_cuda and positions.is_cuda
+    _bf16c(tok, "tok"); _bf16c(pos, "pos")
+    assert tok.dim() == 2 and pos.dim() == 2 and tok.shape[1] == pos.shape[1]
+    out = torch.empty((ids.numel(), tok.shape[1]), dtype=torch.bfloat16, device=tok.device)
+    check(_lib.lib().licv_clip_text_embed(_p(ids), _p(positions), _p(tok), _p(pos), _p(out), ids.numel(), tok.shape[1], tok.shape[0],
+                                          pos.shape[0], _stream(tok)))
+    return out
+
+
+def attn_varlen_causal(qkv: torch.Tensor, cu_seqlens_host: torch.Tensor, cu_seqlens_dev: torch.Tensor, n_heads: int, head_dim: int,
+                       scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal self-attention over packed sequences: qkv (rows >= total, 3 * n_heads * head_dim) bf16 rows [Q | K | V] (row stride
+    qkv.stride(0)), cu_seqlens (n_seq + 1,) int32 once on the host and once on the device -> (total, n_heads * head_dim) bf16.  Into `out`
+    (rows >= total) when given: rows past total are not written."""
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1 and qkv.is_cuda
+    assert cu_seqlens_host.dtype == torch.int32 and not cu_seqlens_host.is_cuda and cu_seqlens_host.is_contiguous() and cu_seqlens_host.dim() == 1
+    assert cu_seqlens_dev.dtype == torch.int32 and cu_seqlens_dev.is_cuda and cu_seqlens_dev.is_contiguous() and cu_seqlens_dev.shape == cu_seqlens_host.shape
+    n_seq = cu_seqlens_host.numel() - 1
+    total = int(cu_seqlens_host[-1]) if n_seq >= 1 else 0
+    E = n_heads * head_dim
+    if n_seq < 1 or total < 1 or total > qkv.shape[0] or qkv.shape[1] < 3 * E:
+        raise _lib.LicvError(f"attn_varlen_causal: cu_seqlens end at {total}, qkv is {tuple(qkv.shape)} for {n_heads} heads of {head_dim}")
+    if out is None:
+        out = torch.empty((total, E), dtype=torch.bfloat16, device=qkv.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape[-1] == E and out.numel() >= total * E
+    check(_lib.lib().licv_attn_varlen_causal(_p(qkv), qkv.stride(0), C.c_void_p(cu_seqlens_host.data_ptr()), _p(cu_seqlens_dev), n_seq, n_heads,
+                                             head_dim, float(scale), _p(out), _stream(qkv)))
+    return out
+
+
+def layernorm_rows(x: torch.Tensor, rows: torch.Tensor, w: torch.Tensor, b: torch.Tensor, eps: float) -> torch.Tensor:
+    """out[j] = LayerNorm(x[rows[j]]): x (n, dim) bf16 (row stride x.stride(0)), rows (m,) int32 on the device -> (m, dim) bf16."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.stride(1) == 1 and x.is_cuda
+    assert rows.dtype == torch.int32 and rows.is_cuda and rows.is_contiguous() and rows.dim() == 1
+    _bf16c(w, "w"); _bf16c(b, "b")
+    assert w.numel() == x.shape[1] and b.numel() == x.shape[1]
+    out = torch.empty((rows.numel(), x.shape[1]), dtype=torch.bfloat16, device=x.device)
+    check(_lib.lib().licv_layernorm_rows_fwd(_p(x), x.stride(0), x.shape[0], _p(rows), _p(w), _p(b), _p(out), rows.numel(), x.shape[1],
+                                             float(eps), _stream(x)))
+    return out
+
+
 # ------------------------------------------------------------------------------------------ image resize (bit-equal to Pillow)
 def resize_images(*args, **kwargs):
     """licv.frontend.resize_images (the resize lives with the image front-end; this name completes the op list)."""

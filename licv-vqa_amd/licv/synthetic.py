@@ -369,3 +369,37 @@ def synth_clip_vision_weights(arch: ClipVisionArch, seed: int = 426, dtype=torch
     norm(vp + "post_layernorm", E)
     lin("visual_projection", a.projection_dim, E)
     return sd
+
+
+def synth_clip_text_weights(arch, seed: int = 426, dtype=torch.bfloat16, device="cpu") -> Dict[str, torch.Tensor]:
+    """Random-init CLIP text tower under the key names of hf CLIPTextModelWithProjection (hf:clip/modeling_clip.py), the distributions of
+    synth_clip_vision_weights: linear and embedding tables ~N(0, 0.02), norm weights ~1 + N(0, 0.1), biases ~N(0, 0.02)."""
+    dev = torch.device(device)
+    gen = torch.Generator(device=dev if dev.type == "cuda" else "cpu")
+    gen.manual_seed(seed)
+    sd: Dict[str, torch.Tensor] = {}
+
+    def lin(name, out_f, in_f, bias=False):
+        sd[name + ".weight"] = _randn((out_f, in_f), 0.02, gen, dev, dtype)
+        if bias:
+            sd[name + ".bias"] = _randn((out_f,), 0.02, gen, dev, dtype)
+
+    def norm(name, dim):
+        sd[name + ".weight"] = _randn((dim,), 0.1, gen, dev, dtype, mean=1.0)
+        sd[name + ".bias"] = _randn((dim,), 0.02, gen, dev, dtype)
+
+    a, E = arch, arch.hidden_size
+    tp = "text_model."
+    sd[tp + "embeddings.token_embedding.weight"] = _randn((a.vocab_size, E), 0.02, gen, dev, dtype)
+    sd[tp + "embeddings.position_embedding.weight"] = _randn((a.max_position_embeddings, E), 0.02, gen, dev, dtype)
+    for i in range(a.num_hidden_layers):
+        p = f"{tp}encoder.layers.{i}."
+        for n in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            lin(p + "self_attn." + n, E, E, True)
+        norm(p + "layer_norm1", E)
+        lin(p + "mlp.fc1", a.intermediate_size, E, True)
+        lin(p + "mlp.fc2", E, a.intermediate_size, True)
+        norm(p + "layer_norm2", E)
+    norm(tp + "final_layer_norm", E)
+    lin("text_projection", a.projection_dim, E)
+    return sd
