@@ -26,10 +26,16 @@ extern "C" {
  * on split-K slices; the gradient all-reduce); 7 = sampled decoding (licv_sample_step, licv_beam_sample_step); 8 = RICE retrieval
  * (licv_topk_ip, licv_l2_normalize_rows, licv_quick_gelu); 9 = image resize on the device (licv_resize_images); still 9 with
  * the CLIP text tower's kernels (licv_clip_text_embed, licv_attn_varlen_causal, licv_layernorm_rows_fwd): they only ADD symbols - no
- * existing entry point changed, so a binding written against 9 keeps working (check_exports still asks for every declared symbol). */
+ * existing entry point changed, so a binding written against 9 keeps working (check_exports still asks for every declared symbol); and still 9 with
+ * constrained decoding: licv_logits_process is a new symbol, and licv_beam_step accepts one new VALUE of an existing field
+ * (logits_dtype = LICV_F32_LOGPROBS) that no earlier caller passes - no struct changed its layout. */
 #define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
+/* A value of licv_beam_step_args.logits_dtype ONLY: fp32 rows that are final log-probabilities.  licv_beam_step is the one entry
+ * that accepts it; every other entry that takes a dtype (licv_beam_sample_step, licv_sample_step, licv_logits_process, ...) checks
+ * for LICV_BF16 / LICV_F32 and answers LICV_E_BADARG.  A new entry that takes a dtype must do the same. */
+enum { LICV_F32_LOGPROBS = 2 };
 enum { LICV_OK = 0, LICV_E_BADARG = -1, LICV_E_UNSUPPORTED = -2, LICV_E_HIP = -3 };
 
 int         licv_version(void);
@@ -381,6 +387,10 @@ int licv_decode_attn(const licv_decode_attn_args* a, void* stream);
  * top 2*nb of (nb x V) per question, running / finished set update, early-stop heuristic, and the loop condition.  State buffers are ping-ponged by the caller (in != out for the token rows). */
 typedef struct {
     const void* logits; int logits_dtype;              /* rows of V logits, bf16 or fp32, row stride ld (elements) */
+    /* logits_dtype = LICV_F32_LOGPROBS ("logprobs_in"): the rows are fp32 FINAL log-probabilities, as licv_logits_process leaves them
+     * with normalize = 1 (hf _beam_search: log_softmax, then the logits processors, then + running score); they may hold -inf.  The
+     * scan ranks x itself and the finish uses lp = x + running score; suppress_eos and all bookkeeping are unchanged.
+     * licv_beam_sample_step rejects it (LICV_E_BADARG). */
     int64_t ld;
     int64_t q_stride_rows, beam_stride_rows;           /* logits row of (question b, beam k) = b*q_stride_rows + k*beam_stride_rows
                                                           (nb, 1 in the loop; 1, 0 right after the prefill: all beams share the row) */
@@ -405,6 +415,42 @@ typedef struct {
 } licv_beam_step_args;
 int64_t licv_beam_step_scratch_bytes(int64_t B, int64_t nb);
 int licv_beam_step(const licv_beam_step_args* a, void* stream);
+
+/* ---- logits processors of hooked generate: transformers 5.x _get_logits_processor (generation/utils.py:1123-1330), in its order:
+ * RepetitionPenaltyLogitsProcessor (generation/logits_process.py:306-413), NoRepeatNGramLogitsProcessor (:1073-1139),
+ * NoBadWordsLogitsProcessor (:1395-1480 on SequenceBiasLogitsProcessor.__call__, :1288-1319), SuppressTokensLogitsProcessor (:1869-1906)
+ * and SuppressTokensAtBeginLogitsProcessor (:1816-1866).  ONE launch per decode step turns B*nb rows of next-token logits into dense
+ * fp32 rows of processed scores: out row r = b*nb + k is made from logits row b*q_stride_rows + k*beam_stride_rows and the token
+ * history ids[r, :cur] (prompt and its pad tokens included; the first P entries are the prompt).
+ *   normalize = 0: the processors act on the fp32 value of the logit (hf _sample, greedy and sampling without beams);
+ *   normalize = 1: on its fp32 log-softmax (x - max) - log(sum exp(x - max)) (hf _beam_search; feed licv_beam_step as LICV_F32_LOGPROBS).
+ * repetition_penalty t (1 = off): every DISTINCT token of the history has its score s replaced by s * t if s < 0, else s / t
+ * (once, however often it occurs).  no_repeat_ngram_size n (0 = off): nothing while cur < n; else ids[i + n - 1] is banned for every
+ * i <= cur - n with ids[i .. i+n-2] == ids[cur-n+1 .. cur-1] (n = 1: every token seen).  Bad words: word w is the tokens
+ * bad_words[bad_offsets[w] .. bad_offsets[w+1]); a one-token word is always banned, a word of length L in its last token when
+ * cur >= L and the row's last L - 1 tokens equal its first L - 1 (hf ignores a word longer than the history; the caller drops a
+ * word equal to [eos] as NoBadWordsLogitsProcessor does).  suppress: always banned.  begin_suppress: banned when cur == P.  A ban
+ * writes -inf and wins over the penalty; every output is ONE IEEE operation on the mode's input value.  Tokens outside [0, V) in
+ * any list or history are ignored.  bad_offsets exists twice: on the device for the kernel, on the HOST for the argument check. */
+typedef struct {
+    const void* logits; int logits_dtype;              /* rows of V logits, bf16 or fp32, row stride ld (elements); V <= 65536 */
+    int64_t ld;
+    int64_t q_stride_rows, beam_stride_rows;           /* as licv_beam_step_args: (nb, 1) = dense rows, (1, 0) = a question's beams share a row */
+    int64_t B, nb, V;                                  /* B*nb output rows */
+    const int64_t* ids; int64_t ids_ld;                /* (B*nb, ids_ld) token history, cur <= ids_ld valid entries per row */
+    int64_t cur, P;
+    float* out; int64_t out_ld;                        /* (B*nb, out_ld >= V) fp32, must not overlap logits */
+    int normalize;
+    float repetition_penalty;                          /* > 0; 1 = off */
+    int64_t no_repeat_ngram_size;                      /* >= 0; 0 = off */
+    const int32_t* bad_words; int64_t bad_words_len;   /* flat tokens of all words (device) */
+    const int32_t* bad_offsets;                        /* (n_bad_words + 1) device */
+    const int32_t* bad_offsets_host;                   /* the same values, HOST pointer: 0 = first, strictly rising, last = bad_words_len */
+    int64_t n_bad_words;
+    const int32_t* suppress; int64_t n_suppress;       /* device */
+    const int32_t* begin_suppress; int64_t n_begin_suppress;
+} licv_logits_process_args;
+int licv_logits_process(const licv_logits_process_args* a, void* stream);
 
 /* ---- sampled decoding (do_sample=True) of hooked generate: transformers 5.x _sample (generation/utils.py:2794-2930) and the
  * do_sample branch of _beam_search (_get_top_k_continuations, :3090-3125, :3388-3420) with the warpers of _get_logits_processor

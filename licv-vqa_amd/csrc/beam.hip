@@ -85,16 +85,19 @@ void beam_scan_k(licv_beam_step_args a, float* __restrict__ stats, float* __rest
         } else {
         float mx = -INFINITY;
         for (int i = tid; i < n; i += BEAM_THREADS) {
-            const float x = a.logits_dtype == LICV_F32 ? reinterpret_cast<const float*>(a.logits)[row * a.ld + i0 + i]
-                                                       : bf2f(reinterpret_cast<const bf16_t*>(a.logits)[row * a.ld + i0 + i]);
+            const float x = a.logits_dtype != LICV_BF16 ? reinterpret_cast<const float*>(a.logits)[row * a.ld + i0 + i]
+                                                        : bf2f(reinterpret_cast<const bf16_t*>(a.logits)[row * a.ld + i0 + i]);
             sx[i] = x;
             mx = fmaxf(mx, x);
         }
+        if (a.logits_dtype == LICV_F32_LOGPROBS) __syncthreads();                 // final log-probabilities: no statistics, x itself is ranked
+        else {
         mx = beam_block_reduce(mx, true, red);              // (its barriers also publish sx)
         float z = 0.f;
         for (int i = tid; i < n; i += BEAM_THREADS) z += expf(sx[i] - mx);
         z = beam_block_reduce(z, false, red);
         if (tid == 0) { stats[slot * 2] = mx; stats[slot * 2 + 1] = z; }
+        }
         if (a.suppress_eos && a.eos >= i0 && a.eos < i0 + n && tid == 0) sx[a.eos - i0] = -INFINITY;   // ranked as -inf, still part of the sum
         __syncthreads();
         }
@@ -149,7 +152,7 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
             for (int k = 0; k < NB; ++k) am = fmaxf(am, sc.bst[((int64_t)b * NB + k) * 4 + 2] + a.run_scores_in[(int64_t)b * NB + k]);
             s_amax = am; s_err = 0;
         }
-    } else if (tid < NB) {
+    } else if (tid < NB && a.logits_dtype != LICV_F32_LOGPROBS) {
         const float* st = stats + ((int64_t)b * NB + tid) * BEAM_CHUNKS * 2;
         float mx = -INFINITY;
         for (int c = 0; c < BEAM_CHUNKS; ++c) mx = fmaxf(mx, st[c * 2]);
@@ -165,6 +168,7 @@ void beam_finish_k(licv_beam_step_args a, const float* __restrict__ stats, const
         const int tok = cand_i[(int64_t)b * NC + i];
         float v;
         if constexpr (SAMPLE) { v = x; lpa[i] = sc.cand_a[(int64_t)b * NC + i]; }
+        else if (a.logits_dtype == LICV_F32_LOGPROBS) v = x + a.run_scores_in[(int64_t)b * NB + beam];
         else v = ((x - s_mx[beam]) - s_lse[beam]) + a.run_scores_in[(int64_t)b * NB + beam];
         if (tok == INT_MAX) v = -INFINITY;
         lpv[i] = v;
@@ -319,7 +323,7 @@ extern "C" int licv_beam_step(const licv_beam_step_args* x, void* stream) {
     LICV_CHECK_ARG(x && x->logits && x->running_in && x->finished_in && x->run_scores_in && x->fin_scores_in && x->is_fin_in && x->improve_in &&
                    x->gen_len_in && x->running_out && x->finished_out && x->run_scores_out && x->fin_scores_out && x->is_fin_out &&
                    x->improve_out && x->gen_len_out && x->beam_src_flat && x->next_tokens && x->flags && x->sync && x->scratch, "beam_step: null pointer");
-    LICV_CHECK_ARG(x->logits_dtype == LICV_BF16 || x->logits_dtype == LICV_F32, "beam_step: bad logits dtype");
+    LICV_CHECK_ARG(x->logits_dtype == LICV_BF16 || x->logits_dtype == LICV_F32 || x->logits_dtype == LICV_F32_LOGPROBS, "beam_step: bad logits dtype");
     LICV_CHECK_ARG(x->nb >= 1 && x->nb <= BEAM_MAX_NB, "beam_step: num_beams %lld outside 1..%d", (long long)x->nb, BEAM_MAX_NB);
     LICV_CHECK_ARG(x->B >= 1 && x->V >= 2 * x->nb && x->ld >= x->V && x->nb * x->V < (1ll << 31), "beam_step: bad batch / vocabulary size");
     LICV_CHECK_ARG(x->V <= (int64_t)BEAM_CHUNKS * BEAM_CHUNK_MAX, "beam_step: vocabulary %lld above the scan's limit %d", (long long)x->V, BEAM_CHUNKS * BEAM_CHUNK_MAX);
@@ -430,6 +434,7 @@ extern "C" int licv_beam_sample_step(const licv_beam_step_args* x, const licv_sa
                    x->gen_len_in && x->running_out && x->finished_out && x->run_scores_out && x->fin_scores_out && x->is_fin_out &&
                    x->improve_out && x->gen_len_out && x->beam_src_flat && x->next_tokens && x->flags && x->sync && x->scratch,
                    "beam_sample_step: null pointer");
+    LICV_CHECK_ARG(x->logits_dtype != LICV_F32_LOGPROBS, "beam_sample_step: logprobs_in (logits processors before the beam-search draw) is not built");
     LICV_CHECK_ARG(x->logits_dtype == LICV_BF16 || x->logits_dtype == LICV_F32, "beam_sample_step: bad logits dtype");
     LICV_CHECK_ARG(x->nb >= 2 && x->nb <= BEAM_MAX_NB, "beam_sample_step: num_beams %lld outside 2..%d", (long long)x->nb, BEAM_MAX_NB);
     LICV_CHECK_ARG(x->B >= 1 && x->V >= 2 * x->nb && x->ld >= x->V && x->nb * x->V < (1ll << 31), "beam_sample_step: bad batch / vocabulary size");

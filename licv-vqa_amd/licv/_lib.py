@@ -18,6 +18,7 @@ LAB_PATH = Path(os.environ.get("LICV_HIP_LAB_LIB", _HERE / "liblicv_hip_lab.so")
 LAB_HEADER = _HERE.parents[1] / "include" / "licv_hip_lab.h"
 
 LICV_BF16, LICV_F32 = 0, 1
+LICV_F32_LOGPROBS = 2     # licv_beam_step_args.logits_dtype only: fp32 rows of final log-probabilities (licv_logits_process, normalize=1)
 ABI_VERSION = 9          # == LICV_ABI_VERSION of include/licv_hip.h this binding was written against (check_exports compares both)
 
 _lib = None
@@ -56,6 +57,16 @@ class BeamStepArgs(C.Structure):
                 ("beam_src_flat", C.c_void_p), ("next_tokens", C.c_void_p), ("flags", C.c_void_p), ("sync", C.c_void_p),
                 ("kv_rows_in", C.c_void_p), ("kv_rows_out", C.c_void_p), ("kv_ld", C.c_int64),
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
+class LogitsProcessArgs(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("logits_dtype", C.c_int), ("ld", C.c_int64), ("q_stride_rows", C.c_int64),
+                ("beam_stride_rows", C.c_int64), ("B", C.c_int64), ("nb", C.c_int64), ("V", C.c_int64),
+                ("ids", C.c_void_p), ("ids_ld", C.c_int64), ("cur", C.c_int64), ("P", C.c_int64),
+                ("out", C.c_void_p), ("out_ld", C.c_int64), ("normalize", C.c_int), ("repetition_penalty", C.c_float),
+                ("no_repeat_ngram_size", C.c_int64), ("bad_words", C.c_void_p), ("bad_words_len", C.c_int64),
+                ("bad_offsets", C.c_void_p), ("bad_offsets_host", C.c_void_p), ("n_bad_words", C.c_int64),
+                ("suppress", C.c_void_p), ("n_suppress", C.c_int64), ("begin_suppress", C.c_void_p), ("n_begin_suppress", C.c_int64)]
 
 
 class SampleParams(C.Structure):
@@ -147,6 +158,7 @@ def lib() -> C.CDLL:
             "licv_attn_select": [I],
             "licv_attn_fwd": [C.POINTER(AttnArgs), P],
             "licv_beam_step": [C.POINTER(BeamStepArgs), P],
+            "licv_logits_process": [C.POINTER(LogitsProcessArgs), P],
             "licv_sample_step": [C.POINTER(SampleStepArgs), C.POINTER(SampleParams), P],
             "licv_beam_sample_step": [C.POINTER(BeamStepArgs), C.POINTER(SampleParams), P],
             "licv_decode_attn": [C.POINTER(DecodeAttnArgs), P],

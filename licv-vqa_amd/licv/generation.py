@@ -106,6 +106,7 @@ class _Idefics2Decoder:
 def generate(engine: IdeficsEngine, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: torch.Tensor,
              image_attention_mask: torch.Tensor, icv: Optional[torch.Tensor] = None,
              hook_layers: Optional[Sequence[int]] = None, max_new_tokens: int = 5, num_beams: int = 1, **kw) -> torch.Tensor:
+    _precheck(engine.arch, num_beams, kw)
     hooks = dict(icv=icv, hook_layers=hook_layers) if icv is not None else {}
     model = _IdeficsDecoder(engine, pixel_values, image_attention_mask, input_ids.shape[0], input_ids.shape[1] + max_new_tokens, hooks, beams=num_beams)
     return _decode(model, engine.arch, input_ids, attention_mask, max_new_tokens=max_new_tokens, num_beams=num_beams, **kw)
@@ -115,6 +116,7 @@ def generate(engine: IdeficsEngine, input_ids: torch.Tensor, attention_mask: tor
 def generate_idefics2(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: Optional[torch.Tensor] = None,
                       pixel_attention_mask: Optional[torch.Tensor] = None, icv: Optional[torch.Tensor] = None,
                       hook_layers: Optional[Sequence[int]] = None, max_new_tokens: int = 5, num_beams: int = 1, **kw) -> torch.Tensor:
+    _precheck(engine.arch, num_beams, kw)
     hooks = dict(icv=icv, hook_layers=hook_layers) if icv is not None else {}
     model = _Idefics2Decoder(engine, pixel_values, pixel_attention_mask, input_ids.shape[0], input_ids.shape[1] + max_new_tokens, hooks, beams=num_beams)
     return _decode(model, engine.arch, input_ids, attention_mask, max_new_tokens=max_new_tokens, num_beams=num_beams, **kw)
@@ -133,14 +135,72 @@ def sample_params(temperature=None, top_k=None, top_p=None, min_p=None, seed=Non
     return p
 
 
+_CONSTRAINT_KEYS = ("repetition_penalty", "no_repeat_ngram_size", "bad_words_ids", "suppress_tokens", "begin_suppress_tokens")
+_BEAM_SAMPLE_CONSTRAINED = ("generate(do_sample=True, num_beams > 1) with repetition_penalty / no_repeat_ngram_size / bad_words_ids / "
+                            "suppress_tokens / begin_suppress_tokens: beam-search multinomial sampling on processed log-probabilities "
+                            "is not built on the native path")
+
+
+def _vocab(a) -> int:
+    return getattr(a, "total_vocab", None) or a.vocab_size
+
+
+def check_constraints(vocab: int, repetition_penalty=None, no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None,
+                      begin_suppress_tokens=None) -> bool:
+    """The logits-processor keywords of `generate`, validated as transformers validates them (hf:generation/logits_process.py
+    RepetitionPenaltyLogitsProcessor.__init__, NoRepeatNGramLogitsProcessor.__init__, NoBadWordsLogitsProcessor._validate_arguments;
+    ids must also lie inside the vocabulary).  Returns whether any of them is on (off: None, penalty 1.0, size 0, an empty list)."""
+    def is_int(t):
+        return isinstance(t, int) and not isinstance(t, bool)
+
+    if repetition_penalty is not None and (not isinstance(repetition_penalty, float) or not repetition_penalty > 0):
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty!r}")
+    if no_repeat_ngram_size is not None and (not is_int(no_repeat_ngram_size) or no_repeat_ngram_size < 0):
+        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {no_repeat_ngram_size!r}")
+    if bad_words_ids is not None:
+        if not isinstance(bad_words_ids, (list, tuple)) or any(not isinstance(w, (list, tuple)) or len(w) == 0 for w in bad_words_ids):
+            raise ValueError(f"`bad_words_ids` has to be a list of non-empty lists of token ids, but is {bad_words_ids!r}")
+        if any(not is_int(t) or not 0 <= t < vocab for w in bad_words_ids for t in w):
+            raise ValueError(f"each token of `bad_words_ids` has to be an integer in [0, {vocab}), but it is {bad_words_ids!r}")
+    for name, lst in (("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens)):
+        if lst is not None and (not isinstance(lst, (list, tuple)) or any(not is_int(t) or not 0 <= t < vocab for t in lst)):
+            raise ValueError(f"`{name}` has to be a list of token ids in [0, {vocab}), but is {lst!r}")
+    return bool((repetition_penalty or 1.0) != 1.0 or no_repeat_ngram_size or bad_words_ids or suppress_tokens or begin_suppress_tokens)
+
+
+def _precheck(a, num_beams, kw):
+    """Bad processor values and the one combination that is not built raise before the model side launches anything."""
+    if check_constraints(_vocab(a), *(kw.get(k) for k in _CONSTRAINT_KEYS)) and kw.get("do_sample") and num_beams > 1:
+        raise NotImplementedError(_BEAM_SAMPLE_CONSTRAINED)
+
+
+def logits_constraints(device, vocab: int, eos: Optional[int], repetition_penalty=None, no_repeat_ngram_size=None, bad_words_ids=None,
+                       suppress_tokens=None, begin_suppress_tokens=None):
+    """The validated keywords as a licv.ops.LogitsConstraints with the lists on the device - or None when every one of them is
+    off: the decode loop then launches and allocates nothing new."""
+    if not check_constraints(vocab, repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens):
+        return None
+    from .ops import LogitsConstraints
+    c = LogitsConstraints(device, 1.0 if repetition_penalty is None else repetition_penalty, no_repeat_ngram_size or 0, bad_words_ids,
+                          suppress_tokens, begin_suppress_tokens, eos=eos)
+    return c if c.active else None                                    # (the only bad word was [eos])
+
+
 def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max_new_tokens: int = 5, num_beams: int = 1,
             length_penalty: float = 1.0, min_new_tokens: int = 0, early_stopping=False,
             eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, do_sample: bool = False,
             temperature: Optional[float] = None, top_k: Optional[int] = None, top_p: Optional[float] = None,
-            min_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
+            min_p: Optional[float] = None, seed: Optional[int] = None, repetition_penalty: Optional[float] = None,
+            no_repeat_ngram_size: Optional[int] = None, bad_words_ids=None, suppress_tokens=None,
+            begin_suppress_tokens=None) -> torch.Tensor:
     dev = input_ids.device
     sampling = sample_params(temperature, top_k, top_p, min_p, seed) if do_sample else None
     eos = a.eos_token_id if eos_token_id is None else eos_token_id
+    # logits processors (csrc/logits_process.hip): None = all off, and then nothing below differs from the unconstrained decode
+    cons = logits_constraints(dev, _vocab(a), eos, repetition_penalty, no_repeat_ngram_size, bad_words_ids, suppress_tokens,
+                              begin_suppress_tokens)
+    if cons is not None and sampling is not None and num_beams > 1:
+        raise NotImplementedError(_BEAM_SAMPLE_CONSTRAINED)
     pad = a.pad_token_id if pad_token_id is None else pad_token_id
     B, P = input_ids.shape
     max_len = P + max_new_tokens
@@ -154,7 +214,7 @@ def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max
         return lp
 
     if nb == 1 and sampling is not None:                              # ---- multinomial sampling (_sample, do_sample): csrc/sample.hip
-        state = SampleState(B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling)
+        state = SampleState(B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling, constraints=cons)
         am = attention_mask
         while True:
             more = state.step(logits)                                 # one device -> host read per step
@@ -170,8 +230,14 @@ def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         am = attention_mask
         cur = P
+        buf = None
         while True:
-            scores = suppress_eos(logits.float(), cur - P)
+            if cons is None:
+                scores = logits.float()
+            else:                                                     # hf _sample: the processors on the fp32 logits, history = seq[:, :cur]
+                from .ops import logits_process
+                buf = scores = logits_process(logits, seq, cur, P, cons, out=buf)
+            scores = suppress_eos(scores, cur - P)
             nxt = scores.argmax(-1)
             nxt = torch.where(unfinished, nxt, torch.full_like(nxt, pad))
             seq[:, cur] = nxt
@@ -194,7 +260,7 @@ def _decode(model, a, input_ids: torch.Tensor, attention_mask: torch.Tensor, max
     model.replicate(nb)
     table = model.kv_rows() if hasattr(model, "kv_rows") and hasattr(model, "reorder_with_rows") else None
     search = BeamSearchState(B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=table,
-                             sampling=sampling)
+                             sampling=sampling, constraints=cons)
     am = attention_mask.repeat_interleave(nb, 0)
     first = True
     while True:
@@ -217,8 +283,13 @@ class BeamSearchState:
     Two copies of every buffer: the kernel gathers rows of the old state into the new one."""
 
     def __init__(self, B, nb, P, max_len, fill, input_ids, eos, length_penalty, early_stopping, min_new_tokens, kv_rows=None,
-                 sampling=None):
+                 sampling=None, constraints=None):
         dev = input_ids.device
+        # constraints: a licv.ops.LogitsConstraints (hf _beam_search: log_softmax, then the logits processors on every running beam's
+        # history, then the search): licv_logits_process with normalize = 1 before each step, its rows into licv_beam_step as
+        # final log-probabilities.  None = today's single call.
+        assert constraints is None or sampling is None, "beam-search multinomial sampling with logits processors is not built"
+        self.constraints, self._lp = constraints, None
         # sampling: a licv._lib.SampleParams (beam-search multinomial sampling through licv_beam_sample_step), None = beam search
         self.sampling = sampling
         self.B, self.nb, self.P, self.max_len, self.cur = B, nb, P, max_len, P
@@ -246,15 +317,30 @@ class BeamSearchState:
         self.kv_rows = kv_rows
         self._kv_rows_next = torch.empty_like(kv_rows) if kv_rows is not None else None
 
-    def step(self, logits: torch.Tensor, shared_rows: bool = False) -> bool:
+    def step(self, logits: torch.Tensor, shared_rows: bool = False, logprobs_in: bool = False) -> bool:
         """logits: (B*nb, V) rows (bf16 or fp32, row stride = stride(0)); shared_rows: (B, V) rows of the prefill that all beams of a
-        question share.  Returns whether the search continues (reads one int32 back)."""
+        question share.  Returns whether the search continues (reads one int32 back).
+        logprobs_in is a TEST HOOK (tests/test_beam_step_logprobs_gpu.py): the rows are fp32 final log-probabilities (-inf allowed)
+        handed straight to licv_beam_step.  The product path never passes it - with `constraints` the pre-pass below makes such rows
+        itself - so build nothing on it."""
         import ctypes as C
         from . import _lib
         from .ops import _dt, _p, _stream, check
         assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == (self.B if shared_rows else self.B * self.nb)
         a = _lib.BeamStepArgs()
         a.logits, a.logits_dtype, a.ld = logits.data_ptr(), _dt(logits), logits.stride(0)
+        if self.constraints is not None:
+            from .ops import logits_process
+            if self._lp is None:
+                self._lp = torch.empty((self.B * self.nb, logits.shape[1]), dtype=torch.float32, device=logits.device)
+            running = self.state[0]["running"]                 # the state the previous step wrote: (B, nb, max_len)
+            # first step: the B shared prefill rows, history = the prompt (all beams of a question hold it); later: every running beam
+            hist, out = (running[:, 0, :], self._lp[:self.B]) if shared_rows else (running.view(self.B * self.nb, self.max_len), self._lp)
+            logits_process(logits, hist, self.cur, self.P, self.constraints, normalize=True, out=out)
+            a.logits, a.logits_dtype, a.ld = out.data_ptr(), _lib.LICV_F32_LOGPROBS, out.stride(0)
+        if logprobs_in:
+            assert logits.dtype == torch.float32 and self.constraints is None
+            a.logits_dtype = _lib.LICV_F32_LOGPROBS
         a.q_stride_rows, a.beam_stride_rows = (1, 0) if shared_rows else (self.nb, 1)
         a.B, a.nb, a.V, a.max_len, a.cur, a.P = self.B, self.nb, logits.shape[1], self.max_len, self.cur, self.P
         a.eos = self.eos
@@ -294,8 +380,11 @@ class SampleState:
     """Device-side state of multinomial sampling without beams (hf GenerationMixin._sample with do_sample=True), advanced by
     `licv_sample_step`: the running (B, max_len) id buffer, the unfinished flags and the loop flag."""
 
-    def __init__(self, B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling):
+    def __init__(self, B, P, max_len, input_ids, eos, pad, min_new_tokens, sampling, constraints=None):
         dev = input_ids.device
+        # constraints: a licv.ops.LogitsConstraints - hf _sample runs the logits processors on the fp32 logits before the warpers:
+        # licv_logits_process (normalize = 0) into an fp32 buffer that licv_sample_step then reads (it ranks -inf correctly)
+        self.constraints, self._lp = constraints, None
         self.B, self.P, self.max_len, self.cur = B, P, max_len, P
         self.eos = -1 if eos is None else int(eos)
         self.pad = int(pad) if pad is not None else (self.eos if self.eos >= 0 else 0)
@@ -313,6 +402,9 @@ class SampleState:
         from . import _lib
         from .ops import _dt, _stream, check
         assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] == self.B
+        if self.constraints is not None:
+            from .ops import logits_process
+            self._lp = logits = logits_process(logits, self.seq, self.cur, self.P, self.constraints, out=self._lp)
         a = _lib.SampleStepArgs()
         a.logits, a.logits_dtype, a.ld = logits.data_ptr(), _dt(logits), logits.stride(0)
         a.B, a.V = self.B, logits.shape[1]

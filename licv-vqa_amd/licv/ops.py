@@ -754,3 +754,60 @@ def resize_images(*args, **kwargs):
     """licv.frontend.resize_images (the resize lives with the image front-end; this name completes the op list)."""
     from . import frontend
     return frontend.resize_images(*args, **kwargs)
+
+
+class LogitsConstraints:
+    """The logits processors of one `generate` call for licv_logits_process (csrc/logits_process.hip): repetition_penalty,
+    no_repeat_ngram_size, bad_words_ids, suppress_tokens, begin_suppress_tokens with transformers' meaning.  The flat lists are
+    uploaded here, once; a bad word equal to `[eos]` is dropped as hf NoBadWordsLogitsProcessor drops it."""
+
+    def __init__(self, device, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, bad_words_ids=None,
+                 suppress_tokens=None, begin_suppress_tokens=None, eos: Optional[int] = None):
+        self.repetition_penalty, self.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
+        words = [list(map(int, w)) for w in (bad_words_ids or []) if not (eos is not None and list(w) == [eos])]
+        offs = [0]
+        for w in words:
+            offs.append(offs[-1] + len(w))
+
+        def up(v):
+            return torch.tensor(v, dtype=torch.int32, device=device) if len(v) else None
+        self.n_bad_words, self.bad_words_len = len(words), offs[-1]
+        self.bad_words, self.bad_offsets = up([t for w in words for t in w]), up(offs if words else [])
+        self.bad_offsets_host = (C.c_int32 * len(offs))(*offs)
+        self.suppress, self.begin_suppress = up(list(map(int, suppress_tokens or []))), up(list(map(int, begin_suppress_tokens or [])))
+
+    @property
+    def active(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.no_repeat_ngram_size > 0 or self.n_bad_words > 0 or self.suppress is not None
+                or self.begin_suppress is not None)
+
+
+def logits_process(logits: torch.Tensor, ids: torch.Tensor, cur: int, P: int, constraints: LogitsConstraints, normalize: bool = False,
+                   nb: int = 1, shared_rows: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """licv_logits_process: rows of next-token logits (bf16 or fp32, row stride = stride(0)) -> dense fp32 rows of processed scores
+    (`normalize`: of their log-softmax, as beam search processes them).  ids: (R, >= cur) int64 token history of every OUTPUT row;
+    R = ids.shape[0] rows come out.  shared_rows: the `nb` beams of a question read one logits row (logits has R / nb rows)."""
+    R, V = ids.shape[0], logits.shape[1]
+    assert logits.dim() == 2 and logits.stride(1) == 1 and ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1
+    assert R % nb == 0 and logits.shape[0] == (R // nb if shared_rows else R)
+    if out is None:
+        out = torch.empty((R, V), dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.shape == (R, V) and out.stride(1) == 1 and out.data_ptr() != logits.data_ptr()
+    c = constraints
+    a = _lib.LogitsProcessArgs()
+    a.logits, a.logits_dtype, a.ld = logits.data_ptr(), _dt(logits), logits.stride(0)
+    a.q_stride_rows, a.beam_stride_rows = (1, 0) if shared_rows else (nb, 1)
+    a.B, a.nb, a.V = R // nb, nb, V
+    a.ids, a.ids_ld, a.cur, a.P = ids.data_ptr(), ids.stride(0), cur, P
+    a.out, a.out_ld, a.normalize = out.data_ptr(), out.stride(0), 1 if normalize else 0
+    a.repetition_penalty, a.no_repeat_ngram_size = c.repetition_penalty, c.no_repeat_ngram_size
+    if c.n_bad_words:
+        a.bad_words, a.bad_words_len, a.n_bad_words = c.bad_words.data_ptr(), c.bad_words_len, c.n_bad_words
+        a.bad_offsets, a.bad_offsets_host = c.bad_offsets.data_ptr(), C.cast(c.bad_offsets_host, C.c_void_p)
+    if c.suppress is not None:
+        a.suppress, a.n_suppress = c.suppress.data_ptr(), c.suppress.numel()
+    if c.begin_suppress is not None:
+        a.begin_suppress, a.n_begin_suppress = c.begin_suppress.data_ptr(), c.begin_suppress.numel()
+    assert cur <= ids.shape[1]
+    check(_lib.lib().licv_logits_process(C.byref(a), _stream(logits)))
+    return out

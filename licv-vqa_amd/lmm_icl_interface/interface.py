@@ -213,8 +213,13 @@ class IdeficsInterface(LMMInterface):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, image_attention_mask=None,
                  max_new_tokens=20, num_beams=1, length_penalty=1.0, min_new_tokens=0, early_stopping=False,
-                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None, **kw):
+                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None,
+                 repetition_penalty=None, no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, **kw):
         sampling = _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, kw)
+        # transformers' logits processors the native path builds (licv.generation.logits_constraints validates them; csrc/logits_process.hip)
+        sampling.update(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                        suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
         return native_generate(self.engine, input_ids.to(self._device), attention_mask.to(self._device),
                                pixel_values.to(self._device), self._image_mask(input_ids, pixel_values, image_attention_mask),
                                max_new_tokens=max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
@@ -290,8 +295,13 @@ class Idefics2Interface(IdeficsInterface):
     @torch.no_grad()
     def generate(self, input_ids=None, attention_mask=None, pixel_values=None, pixel_attention_mask=None,
                  max_new_tokens=20, num_beams=1, length_penalty=1.0, min_new_tokens=0, early_stopping=False,
-                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None, **kw):
+                 eos_token_id=None, pad_token_id=None, do_sample=False, temperature=None, top_k=None, top_p=None, min_p=None,
+                 repetition_penalty=None, no_repeat_ngram_size=None, bad_words_ids=None, suppress_tokens=None,
+                 begin_suppress_tokens=None, **kw):
         sampling = _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, kw)
+        # transformers' logits processors the native path builds (licv.generation.logits_constraints validates them; csrc/logits_process.hip)
+        sampling.update(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size, bad_words_ids=bad_words_ids,
+                        suppress_tokens=suppress_tokens, begin_suppress_tokens=begin_suppress_tokens)
         from licv.generation import generate_idefics2
         dev = self._device
         return generate_idefics2(self.engine, input_ids.to(dev), attention_mask.to(dev),

@@ -436,14 +436,16 @@ def g8_generate_idefics2():
 JITTER_TRIALS = 24
 
 
-def _gen_with_margins(w, icv, batch, num_beams, prompt_len, n_rows, seed0=1000):
+def _gen_with_margins(w, icv, batch, num_beams, prompt_len, n_rows, seed0=1000, gen_kw=None):
     """Reference generate (through the reference's wrapper, its own call shape: ref:inference.py:313,
     ref:config/inference.yaml:26-30) returning the ids plus, per row, how ROBUST that decode is to bf16-level noise:
     the same reference call is repeated JITTER_TRIALS times with every next-token score moved by -1, 0 or +1 bf16 ulp of its own
     magnitude at random (a transformers LogitsProcessor) and the fraction of trials that reproduce the row's ids is stored.
     Two bf16 implementations of the same model differ by one ulp on a few logits per step (measured: the native engine vs this
     reference, max 1 ulp), so a row with stability 1.0 — no candidate comparison of the search sits within two ulp — must be
-    reproduced exactly; rows below 1.0 are the reference's own near-ties (bf16 logits tie EXACTLY on several rows)."""
+    reproduced exactly; rows below 1.0 are the reference's own near-ties (bf16 logits tie EXACTLY on several rows).
+    `gen_kw`: further generate keywords (tools/make_golden_constrained.py: max_new_tokens, the built-in logits processors; the
+    jitter runs after them, and leaves a banned score of -inf as it is)."""
     from transformers import LogitsProcessor, LogitsProcessorList
 
     class Jitter(LogitsProcessor):
@@ -454,11 +456,12 @@ def _gen_with_margins(w, icv, batch, num_beams, prompt_len, n_rows, seed0=1000):
             x = scores.float()
             ulp = torch.exp2(torch.floor(torch.log2(x.abs().clamp_min(1e-20))) - 7)
             step = torch.randint(-1, 2, x.shape, generator=self.g).float()
-            return (x + step * ulp).to(scores.dtype)
+            return torch.where(torch.isinf(x), x, x + step * ulp).to(scores.dtype)
 
     plain = dict(max_new_tokens=5, do_sample=False)
     if num_beams > 1:
         plain.update(num_beams=num_beams, length_penalty=0.0, min_new_tokens=0)
+    plain.update(gen_kw or {})
     with torch.inference_mode():
         ids = w.generate(icv=icv, **batch, **plain)
         hits = torch.zeros(n_rows)
@@ -570,12 +573,12 @@ def _select_stable(run_study, n_pool: int, n_keep: int, trials: int):
     raise RuntimeError("could not find a batch that is stable in every mode")
 
 
-def _gen_with_margins_seeded(w, icv, batch, num_beams, n_rows, seed0, trials):
+def _gen_with_margins_seeded(w, icv, batch, num_beams, n_rows, seed0, trials, gen_kw=None):
     global JITTER_TRIALS
     old = JITTER_TRIALS
     JITTER_TRIALS = trials
     try:
-        return _gen_with_margins(w, icv, batch, num_beams, 0, n_rows, seed0=seed0)
+        return _gen_with_margins(w, icv, batch, num_beams, 0, n_rows, seed0=seed0, gen_kw=gen_kw)
     finally:
         JITTER_TRIALS = old
 
