@@ -467,7 +467,14 @@ __device__ __forceinline__ void wait_vmcnt4(int n4) {              // waits vmcn
     }
 }
 
-__device__ __forceinline__ uint32_t pack_bf2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
+// out = bf16(residual + y0) on the four dwords of a lane's block, pair by pair as the residual was loaded: the halves stay where they
+// are (v_pk_add_f32, one v_cvt_pk_bf16_f32), nothing to re-pair afterwards
+__device__ __forceinline__ u32x4 add_res_bf2x4(const u32x4& res, const u32x4& y0) {
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(unpack_bf2(res[e]) + unpack_bf2(y0[e]));
+    return o;
+}
 
 // rows (16-lane groups) 1 and 3 of `a` trade places with rows 0 and 2 of `b`: afterwards an even-row lane holds
 // {its own a, its odd neighbour's a} and an odd-row lane {its even neighbour's b, its own b}
@@ -654,38 +661,28 @@ void gemm_bf16_flow_k(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* _
                     constexpr int i = decltype(ic)::value;
                     static_for<0, 2>([&](auto pc) {
                         constexpr int p = decltype(pc)::value;
-                        float y[2][4];
-                        if constexpr (EPI == 1) {                       // erf GELU, two values per packed instruction
+                        f32x2 y[4];                                     // pair 2 h + d: columns 2 d, 2 d + 1 of accumulator block 2 p + h
 #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                        for (int h = 0; h < 2; ++h)
 #pragma unroll
-                                for (int r = 0; r < 4; r += 2) {
-                                    const f32x2 g2 = gelu_erf_fast2(f32x2{rbf(acc[i][2 * p + h][r] + bv[2 * p + h][r]),
-                                                                          rbf(acc[i][2 * p + h][r + 1] + bv[2 * p + h][r + 1])});
-                                    y[h][r] = g2[0]; y[h][r + 1] = g2[1];
-                                }
-                        } else {
+                            for (int d = 0; d < 2; ++d)
+                                y[2 * h + d] = f32x2{acc[i][2 * p + h][2 * d], acc[i][2 * p + h][2 * d + 1]} + f32x2{bv[2 * p + h][2 * d], bv[2 * p + h][2 * d + 1]};
+                        if constexpr (EPI == 1) {                       // erf GELU on the block's four pairs at once
+                            f32x2 x[4];
 #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                            for (int e = 0; e < 4; ++e) x[e] = rbf2(y[e]);
+                            gelu_erf_fast2x4(x, y);
+                        } else if constexpr (EPI == 2 || EPI == 3) {
 #pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const float v = acc[i][2 * p + h][r] + bv[2 * p + h][r];
-                                    y[h][r] = (EPI == 0 || EPI == 5) ? v : act_apply(rbf(v), EPI);
-                                }
+                            for (int e = 0; e < 4; ++e) y[e] = act_bf2<EPI>(y[e]);
                         }
-                        uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                        uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                        uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                        uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                         swap16(a0, b0);
                         swap16(a1, b1);
                         u32x4 outv = u32x4{a0, a1, b0, b1};         // 8 consecutive columns of y0 = bf16(acc + bias)
-                        if constexpr (EPI == 5) {                   // out = bf16(residual + y0), as epilogue_rows_res does from the LDS image
-                            float q[8], t[8], z[8];
-                            unpack8(rres[i & 3][p], q);
-                            unpack8(outv, t);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) z[e] = q[e] + t[e];
-                            outv = pack8(z);
-                        }
+                        if constexpr (EPI == 5)                     // out = bf16(residual + y0), as epilogue_rows_res does from the LDS image
+                            outv = add_res_bf2x4(rres[i & 3][p], outv);
                         __builtin_amdgcn_raw_buffer_store_b128(outv, crs, off0 + (uint32_t)(i * 16 * ldc * 2 + p * 64), 0, 0);
                         if constexpr (EPI == 5 && i < 4)            // this block's residual registers are free: the same block of the lower half
                             rres[i][p] = __builtin_amdgcn_raw_buffer_load_b128(rrs, roff0 + (uint32_t)((i + 4) * 16 * ld_res * 2 + p * 64), 0, 0);
@@ -701,14 +698,14 @@ void gemm_bf16_flow_k(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* _
                 const uint32_t off0 = (uint32_t)(((cm0 + wm * 128 + fr) * ldc + (colbase >> 1) + (fq & 1) * 16 + (fq >> 1) * 8) * 2);
                 static_for<0, 8>([&](auto ic) {
                     constexpr int i = decltype(ic)::value;
-                    float y[2][4];
+                    f32x2 y[4];
 #pragma unroll
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            y[h][r] = rbf(silu_fast(rbf(acc[i][2 * h][r]))) * rbf(acc[i][2 * h + 1][r]);
-                    uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                    uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                        for (int d = 0; d < 2; ++d)
+                            y[2 * h + d] = swiglu_bf2(f32x2{acc[i][2 * h][2 * d], acc[i][2 * h][2 * d + 1]}, f32x2{acc[i][2 * h + 1][2 * d], acc[i][2 * h + 1][2 * d + 1]});
+                    uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                    uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                     swap16(a0, b0);
                     swap16(a1, b1);
                     __builtin_amdgcn_raw_buffer_store_b128(u32x4{a0, a1, b0, b1}, crs, off0 + (uint32_t)(i * 16 * ldc * 2), 0, 0);
@@ -989,28 +986,26 @@ void gemm_bf16_flow64_k(const bf16_t* __restrict__ A, int64_t lda, const bf16_t*
                     constexpr int i = decltype(ic)::value;
                     static_for<0, 4>([&](auto pc) {
                         constexpr int p = decltype(pc)::value;
-                        float y[2][4], c[2][4];
+                        float c[2][4];
                         take(std::integral_constant<int, 8 * i + 2 * p>{}, c[0]);
                         take(std::integral_constant<int, 8 * i + 2 * p + 1>{}, c[1]);
-                        if constexpr (EPI == 1) {                       // erf GELU, two values per packed instruction
+                        f32x2 y[4];                                     // pair 2 h + d: columns 2 d, 2 d + 1 of accumulator block 2 p + h
     #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                        for (int h = 0; h < 2; ++h)
     #pragma unroll
-                                for (int r = 0; r < 4; r += 2) {
-                                    const f32x2 g2 = gelu_erf_fast2(f32x2{rbf(c[h][r] + bv[2 * p + h][r]), rbf(c[h][r + 1] + bv[2 * p + h][r + 1])});
-                                    y[h][r] = g2[0]; y[h][r + 1] = g2[1];
-                                }
-                        } else {
+                            for (int d = 0; d < 2; ++d)
+                                y[2 * h + d] = f32x2{c[h][2 * d], c[h][2 * d + 1]} + f32x2{bv[2 * p + h][2 * d], bv[2 * p + h][2 * d + 1]};
+                        if constexpr (EPI == 1) {                       // erf GELU on the block's four pairs at once
+                            f32x2 x[4];
     #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                            for (int e = 0; e < 4; ++e) x[e] = rbf2(y[e]);
+                            gelu_erf_fast2x4(x, y);
+                        } else if constexpr (EPI == 2 || EPI == 3) {
     #pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const float v = c[h][r] + bv[2 * p + h][r];
-                                    y[h][r] = (EPI == 0 || EPI == 5) ? v : act_apply(rbf(v), EPI);
-                                }
+                            for (int e = 0; e < 4; ++e) y[e] = act_bf2<EPI>(y[e]);
                         }
-                        uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                        uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                        uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                        uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                         swap16(a0, b0);
                         swap16(a1, b1);
                         u32x4 outv = u32x4{a0, a1, b0, b1};         // 8 consecutive columns of y0 = bf16(acc + bias)
@@ -1020,12 +1015,7 @@ void gemm_bf16_flow64_k(const bf16_t* __restrict__ A, int64_t lda, const bf16_t*
                             __builtin_amdgcn_sched_barrier(0);
                             asm volatile("s_waitcnt vmcnt(%0)" :: "i"(younger) : "memory");
                             __builtin_amdgcn_sched_barrier(0);
-                            float q[8], tt[8], z[8];
-                            unpack8(rres[bb & 7], q);
-                            unpack8(outv, tt);
-    #pragma unroll
-                            for (int e = 0; e < 8; ++e) z[e] = q[e] + tt[e];
-                            outv = pack8(z);
+                            outv = add_res_bf2x4(rres[bb & 7], outv);
                         }
                         __builtin_amdgcn_raw_buffer_store_b128(outv, crs, off0 + (uint32_t)(i * 16 * ldc * 2 + p * 64), 0, 0);
                         if constexpr (EPI == 5 && 4 * i + p + 8 < 32) {
@@ -1043,18 +1033,19 @@ void gemm_bf16_flow64_k(const bf16_t* __restrict__ A, int64_t lda, const bf16_t*
                     constexpr int i = decltype(ic)::value;
                     static_for<0, 2>([&](auto qc) {
                         constexpr int q = decltype(qc)::value;
-                        float y[2][4], c[4][4];
+                        float c[4][4];
                         take(std::integral_constant<int, 8 * i + 4 * q>{}, c[0]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 1>{}, c[1]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 2>{}, c[2]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 3>{}, c[3]);
+                        f32x2 y[4];
     #pragma unroll
                         for (int h = 0; h < 2; ++h)
     #pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                y[h][r] = rbf(silu_fast(rbf(c[2 * h][r]))) * rbf(c[2 * h + 1][r]);
-                        uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                        uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                            for (int d = 0; d < 2; ++d)
+                                y[2 * h + d] = swiglu_bf2(f32x2{c[2 * h][2 * d], c[2 * h][2 * d + 1]}, f32x2{c[2 * h + 1][2 * d], c[2 * h + 1][2 * d + 1]});
+                        uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                        uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                         swap16(a0, b0);
                         swap16(a1, b1);
                         __builtin_amdgcn_raw_buffer_store_b128(u32x4{a0, a1, b0, b1}, crs, off0 + (uint32_t)(i * 16 * ldc * 2 + q * 64), 0, 0);
@@ -1353,7 +1344,7 @@ void gemm_fp8_flow64_k(const char* __restrict__ A, int64_t lda, const char* __re
                     constexpr int i = decltype(ic)::value;
                     static_for<0, 4>([&](auto pc) {
                         constexpr int p = decltype(pc)::value;
-                        float y[2][4], c[2][4];
+                        float c[2][4];
                         take(std::integral_constant<int, 8 * i + 2 * p>{}, c[0]);
                         take(std::integral_constant<int, 8 * i + 2 * p + 1>{}, c[1]);
                         float sc[2][4], bb[2][4];                       // a_scale[m] * w_scale[n] is applied as (acc * a) * w, like the 8-wave kernel
@@ -1362,25 +1353,23 @@ void gemm_fp8_flow64_k(const char* __restrict__ A, int64_t lda, const char* __re
                             sc[e8 >> 2][e8 & 3] = swf(std::integral_constant<int, 8 * p + e8>{});
                             bb[e8 >> 2][e8 & 3] = bvf(std::integral_constant<int, 8 * p + e8>{});
                         });
-                        if constexpr (EPI == 1) {                       // erf GELU, two values per packed instruction
+                        f32x2 y[4];                                     // pair 2 h + d: columns 2 d, 2 d + 1 of accumulator block 2 p + h
     #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                        for (int h = 0; h < 2; ++h)
     #pragma unroll
-                                for (int r = 0; r < 4; r += 2) {
-                                    const f32x2 g2 = gelu_erf_fast2(f32x2{rbf(c[h][r] * sar[i] * sc[h][r] + bb[h][r]), rbf(c[h][r + 1] * sar[i] * sc[h][r + 1] + bb[h][r + 1])});
-                                    y[h][r] = g2[0]; y[h][r + 1] = g2[1];
-                                }
-                        } else {
+                            for (int d = 0; d < 2; ++d)      // C = (Aq . Wq^T) * a_scale[m] * w_scale[n] (+ bias)
+                                y[2 * h + d] = f32x2{c[h][2 * d], c[h][2 * d + 1]} * sar[i] * f32x2{sc[h][2 * d], sc[h][2 * d + 1]} + f32x2{bb[h][2 * d], bb[h][2 * d + 1]};
+                        if constexpr (EPI == 1) {                       // erf GELU on the block's four pairs at once
+                            f32x2 x[4];
     #pragma unroll
-                            for (int h = 0; h < 2; ++h)
+                            for (int e = 0; e < 4; ++e) x[e] = rbf2(y[e]);
+                            gelu_erf_fast2x4(x, y);
+                        } else if constexpr (EPI == 2 || EPI == 3) {
     #pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const float v = c[h][r] * sar[i] * sc[h][r] + bb[h][r];     // C = (Aq . Wq^T) * a_scale[m] * w_scale[n] (+ bias)
-                                    y[h][r] = (EPI == 0 || EPI == 5) ? v : act_apply(rbf(v), EPI);
-                                }
+                            for (int e = 0; e < 4; ++e) y[e] = act_bf2<EPI>(y[e]);
                         }
-                        uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                        uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                        uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                        uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                         swap16(a0, b0);
                         swap16(a1, b1);
                         u32x4 outv = u32x4{a0, a1, b0, b1};         // 8 consecutive columns of y0 = bf16(acc + bias)
@@ -1390,12 +1379,7 @@ void gemm_fp8_flow64_k(const char* __restrict__ A, int64_t lda, const char* __re
                             __builtin_amdgcn_sched_barrier(0);
                             asm volatile("s_waitcnt vmcnt(%0)" :: "i"(younger) : "memory");
                             __builtin_amdgcn_sched_barrier(0);
-                            float q[8], tt[8], z[8];
-                            unpack8(rres[bb & 7], q);
-                            unpack8(outv, tt);
-    #pragma unroll
-                            for (int e = 0; e < 8; ++e) z[e] = q[e] + tt[e];
-                            outv = pack8(z);
+                            outv = add_res_bf2x4(rres[bb & 7], outv);
                         }
                         __builtin_amdgcn_raw_buffer_store_b128(outv, crs, off0 + (uint32_t)(i * 16 * ldc * 2 + p * 64), 0, 0);
                         if constexpr (EPI == 5 && 4 * i + p + 8 < 32) {
@@ -1416,20 +1400,22 @@ void gemm_fp8_flow64_k(const char* __restrict__ A, int64_t lda, const char* __re
                     constexpr int i = decltype(ic)::value;
                     static_for<0, 2>([&](auto qc) {
                         constexpr int q = decltype(qc)::value;
-                        float y[2][4], c[4][4];
+                        float c[4][4];
                         take(std::integral_constant<int, 8 * i + 4 * q>{}, c[0]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 1>{}, c[1]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 2>{}, c[2]);
                         take(std::integral_constant<int, 8 * i + 4 * q + 3>{}, c[3]);
                         float sc[4][4];
                         static_for<0, 16>([&](auto ec) { constexpr int e16 = decltype(ec)::value; sc[e16 >> 2][e16 & 3] = swf(std::integral_constant<int, 16 * q + e16>{}); });
+                        f32x2 y[4];
     #pragma unroll
                         for (int h = 0; h < 2; ++h)
     #pragma unroll
-                            for (int r = 0; r < 4; ++r)
-                                y[h][r] = rbf(silu_fast(rbf(c[2 * h][r] * sar[i] * sc[2 * h][r]))) * rbf(c[2 * h + 1][r] * sar[i] * sc[2 * h + 1][r]);
-                        uint32_t a0 = pack_bf2(y[0][0], y[0][1]), a1 = pack_bf2(y[0][2], y[0][3]);
-                        uint32_t b0 = pack_bf2(y[1][0], y[1][1]), b1 = pack_bf2(y[1][2], y[1][3]);
+                            for (int d = 0; d < 2; ++d)
+                                y[2 * h + d] = swiglu_bf2(f32x2{c[2 * h][2 * d], c[2 * h][2 * d + 1]} * sar[i] * f32x2{sc[2 * h][2 * d], sc[2 * h][2 * d + 1]},
+                                                          f32x2{c[2 * h + 1][2 * d], c[2 * h + 1][2 * d + 1]} * sar[i] * f32x2{sc[2 * h + 1][2 * d], sc[2 * h + 1][2 * d + 1]});
+                        uint32_t a0 = pack_bf2(y[0]), a1 = pack_bf2(y[1]);
+                        uint32_t b0 = pack_bf2(y[2]), b1 = pack_bf2(y[3]);
                         swap16(a0, b0);
                         swap16(a1, b1);
                         __builtin_amdgcn_raw_buffer_store_b128(u32x4{a0, a1, b0, b1}, crs, off0 + (uint32_t)(i * 16 * ldc * 2 + q * 64), 0, 0);

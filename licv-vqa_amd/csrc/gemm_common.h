@@ -68,41 +68,61 @@ __device__ __forceinline__ float gelu_erf_fast(float x) {
     }
     return y;
 }
-// The same GELU on two values at once: identical operations per element, written on 2-vectors so they issue as v_pk_mul_f32 /
-// v_pk_fma_f32 / v_pk_add_f32 - the epilogue of the fc1 GEMM carries 128 of these per lane and tile.  The tail branch is taken
-// by the whole wave when any lane needs it.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 gelu_erf_fast2(f32x2 x) {
-    const f32x2 z = x * 0.70710678118654752440f;
-    const f32x2 zc = f32x2{__builtin_amdgcn_fmed3f(z[0], -GELU_ZM, GELU_ZM), __builtin_amdgcn_fmed3f(z[1], -GELU_ZM, GELU_ZM)};
-    const f32x2 u = zc * zc;
-    f32x2 p = f32x2{2.258253176e-07f, 2.258253176e-07f};
-    p = __builtin_elementwise_fma(p, u, f32x2{-6.468885658e-06f, -6.468885658e-06f});
-    p = __builtin_elementwise_fma(p, u, f32x2{8.784283273e-05f, 8.784283273e-05f});
-    p = __builtin_elementwise_fma(p, u, f32x2{-7.748150965e-04f, -7.748150965e-04f});
-    p = __builtin_elementwise_fma(p, u, f32x2{5.104614887e-03f, 5.104614887e-03f});
-    p = __builtin_elementwise_fma(p, u, f32x2{-2.676485851e-02f, -2.676485851e-02f});
-    p = __builtin_elementwise_fma(p, u, f32x2{1.127952486e-01f, 1.127952486e-01f});
-    p = __builtin_elementwise_fma(p, u, f32x2{-3.761198521e-01f, -3.761198521e-01f});
-    p = __builtin_elementwise_fma(p, u, f32x2{1.128379107e+00f, 1.128379107e+00f});
-    const f32x2 h = 0.5f * x;
-    f32x2 y = h * (1.0f + zc * p);
-    if (__any((z[0] < -GELU_ZM) | (z[1] < -GELU_ZM))) {
-        const f32x2 az = -z;
-        const f32x2 sm = az - GELU_ZM;
-        const f32x2 s = f32x2{__builtin_amdgcn_fmed3f(sm[0], 0.0f, 2.4f), __builtin_amdgcn_fmed3f(sm[1], 0.0f, 2.4f)};
-        f32x2 q = f32x2{4.732637171e-05f, 4.732637171e-05f};
-        q = __builtin_elementwise_fma(q, s, f32x2{-5.468023592e-04f, -5.468023592e-04f});
-        q = __builtin_elementwise_fma(q, s, f32x2{2.993027214e-03f, 2.993027214e-03f});
-        q = __builtin_elementwise_fma(q, s, f32x2{-1.105889119e-02f, -1.105889119e-02f});
-        q = __builtin_elementwise_fma(q, s, f32x2{3.343209252e-02f, 3.343209252e-02f});
-        q = __builtin_elementwise_fma(q, s, f32x2{-9.172994643e-02f, -9.172994643e-02f});
-        q = __builtin_elementwise_fma(q, s, f32x2{2.355919182e-01f, 2.355919182e-01f});
-        const f32x2 a2 = az * az;
-        const f32x2 t = h * (q * f32x2{__expf(-a2[0]), __expf(-a2[1])});
-        y = f32x2{z[0] < -GELU_ZM ? t[0] : y[0], z[1] < -GELU_ZM ? t[1] : y[1]};
+// The same GELU on a lane's block of four pairs (the eight values of one 16-byte store of the register-direct epilogues; the fc1 GEMM
+// carries 32 such blocks per lane and tile): identical operations per element, written on 2-vectors so they issue as v_pk_mul_f32 /
+// v_pk_fma_f32 / v_pk_add_f32, and as straight-line code - the four Horner chains advance side by side, so a dependent v_pk_fma_f32
+// does not wait out its predecessor.  ONE test (the minimum z of the eight values) guards the tail, taken by the whole wave when any
+// lane needs it; inside it the tail is still selected per element, from the same operations and constants as the scalar form:
+// bit-identical to it, whatever mix of tail and non-tail values a block holds.  (The earlier pair-at-a-time form tested each pair:
+// 128 basic blocks per tile, nothing interleaved across them, an s_nop behind every fma.)  f32x2: common.h.
+__device__ __forceinline__ void gelu_erf_fast2x4(const f32x2 (&x)[4], f32x2 (&y)[4]) {
+    f32x2 z[4], zc[4], u[4], p[4], h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        z[k] = x[k] * 0.70710678118654752440f;
+        zc[k] = f32x2{__builtin_amdgcn_fmed3f(z[k][0], -GELU_ZM, GELU_ZM), __builtin_amdgcn_fmed3f(z[k][1], -GELU_ZM, GELU_ZM)};
+        u[k] = zc[k] * zc[k];
+        p[k] = f32x2{2.258253176e-07f, 2.258253176e-07f};
     }
-    return y;
+#define GELU_STEP(v, t, c) _Pragma("unroll") for (int k = 0; k < 4; ++k) v[k] = __builtin_elementwise_fma(v[k], t[k], f32x2{c, c})
+    GELU_STEP(p, u, -6.468885658e-06f);
+    GELU_STEP(p, u, 8.784283273e-05f);
+    GELU_STEP(p, u, -7.748150965e-04f);
+    GELU_STEP(p, u, 5.104614887e-03f);
+    GELU_STEP(p, u, -2.676485851e-02f);
+    GELU_STEP(p, u, 1.127952486e-01f);
+    GELU_STEP(p, u, -3.761198521e-01f);
+    GELU_STEP(p, u, 1.128379107e+00f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        h[k] = 0.5f * x[k];
+        y[k] = h[k] * (1.0f + zc[k] * p[k]);
+    }
+    // fminf drops a NaN operand and NaN < c is false: the test is the `or` of the eight per-element tests
+    const float zmin = fminf(fminf(fminf(z[0][0], z[0][1]), fminf(z[1][0], z[1][1])), fminf(fminf(z[2][0], z[2][1]), fminf(z[3][0], z[3][1])));
+    if (__any(zmin < -GELU_ZM)) {
+        f32x2 az[4], s[4], q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            az[k] = -z[k];
+            const f32x2 sm = az[k] - GELU_ZM;
+            s[k] = f32x2{__builtin_amdgcn_fmed3f(sm[0], 0.0f, 2.4f), __builtin_amdgcn_fmed3f(sm[1], 0.0f, 2.4f)};
+            q[k] = f32x2{4.732637171e-05f, 4.732637171e-05f};
+        }
+        GELU_STEP(q, s, -5.468023592e-04f);
+        GELU_STEP(q, s, 2.993027214e-03f);
+        GELU_STEP(q, s, -1.105889119e-02f);
+        GELU_STEP(q, s, 3.343209252e-02f);
+        GELU_STEP(q, s, -9.172994643e-02f);
+        GELU_STEP(q, s, 2.355919182e-01f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x2 a2 = az[k] * az[k];
+            const f32x2 t = h[k] * (q[k] * f32x2{__expf(-a2[0]), __expf(-a2[1])});
+            y[k] = f32x2{z[k][0] < -GELU_ZM ? t[0] : y[k][0], z[k][1] < -GELU_ZM ? t[1] : y[k][1]};
+        }
+    }
+#undef GELU_STEP
 }
 __device__ __forceinline__ float act_apply(float y, int act) {
     switch (act) {
@@ -115,6 +135,18 @@ __device__ __forceinline__ float act_apply(float y, int act) {
     }
 }
 __device__ __forceinline__ float silu_fast(float v) { return v * fast_rcp(1.0f + __expf(-v)); }
+// Register-direct epilogues, on the pairs a lane holds (the rounding points of the unfused bf16 ops, two values per conversion):
+// SwiGLU of two gate / up accumulator pairs: bf16(silu(bf16(g))) * bf16(u), to be rounded by the caller's pack_bf2
+__device__ __forceinline__ f32x2 swiglu_bf2(f32x2 g, f32x2 u) {
+    const f32x2 gr = rbf2(g);
+    return rbf2(f32x2{silu_fast(gr[0]), silu_fast(gr[1])}) * rbf2(u);
+}
+// activation ACT (2 tanh-GELU, 3 ReLU) of bf16(v), per element
+template <int ACT>
+__device__ __forceinline__ f32x2 act_bf2(f32x2 v) {
+    const f32x2 r = rbf2(v);
+    return f32x2{act_apply(r[0], ACT), act_apply(r[1], ACT)};
+}
 
 __device__ __forceinline__ int lds_off(int row, int chunk) {       // bytes within a [rows][64] bf16 tile
     return row * 128 + ((chunk ^ (row & 7)) << 4);
@@ -237,7 +269,7 @@ __device__ __noinline__ void epilogue_rows_generic(const GemmEpi& ep, void* __re
             if (nv == 8) {
                 u32x4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (uint32_t)f2bf(y[2 * e]) | ((uint32_t)f2bf(y[2 * e + 1]) << 16);
+                for (int e = 0; e < 4; ++e) o[e] = pack_bf2(y[2 * e], y[2 * e + 1]);
                 *reinterpret_cast<u32x4*>(cp) = o;
             } else for (int e = 0; e < nv; ++e) cp[e] = f2bf(y[e]);
         }
@@ -268,7 +300,7 @@ __device__ __forceinline__ void unpack8(const u32x4& v, float (&y)[8]) {
 __device__ __forceinline__ u32x4 pack8(const float (&y)[8]) {
     u32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (uint32_t)f2bf(y[2 * e]) | ((uint32_t)f2bf(y[2 * e + 1]) << 16);
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf2(y[2 * e], y[2 * e + 1]);
     return o;
 }
 __device__ __forceinline__ void store_bf16_row(bf16_t* cp, const float (&y)[8], int nv) {
@@ -509,11 +541,11 @@ __device__ __forceinline__ void epilogue_image(floatx4 (&acc)[MT][NT], const Gem
                 constexpr int j = decltype(jc)::value;
                 uint2 u;
                 if (SCALED) {       // fp8 operands: C = (Aq . Wq^T) * a_scale[m] * w_scale[n]
-                    u.x = (uint32_t)f2bf(acc[i][j][0] * rs * cs[j][0] + bv[j][0]) | ((uint32_t)f2bf(acc[i][j][1] * rs * cs[j][1] + bv[j][1]) << 16);
-                    u.y = (uint32_t)f2bf(acc[i][j][2] * rs * cs[j][2] + bv[j][2]) | ((uint32_t)f2bf(acc[i][j][3] * rs * cs[j][3] + bv[j][3]) << 16);
-                } else {
-                    u.x = (uint32_t)f2bf(acc[i][j][0] + bv[j][0]) | ((uint32_t)f2bf(acc[i][j][1] + bv[j][1]) << 16);
-                    u.y = (uint32_t)f2bf(acc[i][j][2] + bv[j][2]) | ((uint32_t)f2bf(acc[i][j][3] + bv[j][3]) << 16);
+                    u.x = pack_bf2(f32x2{acc[i][j][0], acc[i][j][1]} * rs * f32x2{cs[j][0], cs[j][1]} + f32x2{bv[j][0], bv[j][1]});
+                    u.y = pack_bf2(f32x2{acc[i][j][2], acc[i][j][3]} * rs * f32x2{cs[j][2], cs[j][3]} + f32x2{bv[j][2], bv[j][3]});
+                } else {            // pair-wise: one v_pk_add_f32 and one v_cvt_pk_bf16_f32 per dword
+                    u.x = pack_bf2(f32x2{acc[i][j][0], acc[i][j][1]} + f32x2{bv[j][0], bv[j][1]});
+                    u.y = pack_bf2(f32x2{acc[i][j][2], acc[i][j][3]} + f32x2{bv[j][2], bv[j][3]});
                 }
                 *reinterpret_cast<uint2*>(smem + (rl + i * 16) * YS + (wcol0 + j * 16 + cq) * 2) = u;
             });
