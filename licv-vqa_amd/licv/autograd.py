@@ -14,6 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import ops
+from .blocks import logits_view
 
 
 def _rows2d(logits: torch.Tensor) -> torch.Tensor:
@@ -23,7 +24,7 @@ def _rows2d(logits: torch.Tensor) -> torch.Tensor:
     B, S, V = logits.shape
     if logits.stride(2) != 1 or logits.stride(0) != S * logits.stride(1):
         logits = logits.contiguous()
-    return logits.as_strided((B * S, V), (logits.stride(1), 1))
+    return logits.view(B * S, V)                                     # dims 0 and 1 merge: stride(0) == S * stride(1)
 
 
 def _padded_grad(shape, device):
@@ -34,7 +35,7 @@ def _padded_grad(shape, device):
         rows *= int(d)
     ld = (V + 7) // 8 * 8
     buf = torch.zeros((rows, ld), dtype=torch.bfloat16, device=device)
-    view = buf.as_strided(tuple(shape), (shape[1] * ld, ld, 1)) if len(shape) == 3 else buf[:, :V]
+    view = logits_view(buf[:, :V], shape[0], shape[1]) if len(shape) == 3 else buf[:, :V]
     return buf, view
 
 
@@ -48,10 +49,7 @@ class HookedStudentFn(torch.autograd.Function):
         rows = logits_rows if logits_rows is not None else torch.arange(B * S, device=dev)
         logits, st = student.forward(**inputs, icv=icv.detach(), hook_layers=list(hook_layers), alpha=None, logits_rows=rows)
         ctx.student, ctx.st = student, st
-        if logits_rows is None:
-            V = logits.shape[-1]
-            logits = logits.as_strided((B, S, V), (S * logits.stride(0), logits.stride(0), 1))
-        return logits
+        return logits_view(logits, B, S) if logits_rows is None else logits
 
     @staticmethod
     def backward(ctx, dlogits: torch.Tensor):

@@ -19,8 +19,8 @@ from typing import Dict, NamedTuple, Optional, Tuple
 import torch
 
 from . import ops
+from .blocks import bf16_on, dense_attend, encoder_layer_, load_encoder_layers, pad_cols
 from .config import ClipTextArch, ClipVisionArch
-from .idefics_engine import _bf, _pad_cols, _VitLayer
 
 
 def clip_vision_state(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -47,22 +47,15 @@ class ClipVisionEngine:
             raise RuntimeError("ClipVisionEngine runs on the GPU only (liblicv_hip has no CPU fallback)")
         sd = clip_vision_state(state_dict)
         self.arch, self.device = a, dev
-        g = lambda k: _bf(sd[k], dev)
+        g = lambda k: bf16_on(sd[k], dev)
         vp = "vision_model."
         self.patch_ld = (3 * a.patch_size * a.patch_size + 63) // 64 * 64
-        self.patch_w = _pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
+        self.patch_w = pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
         self.cls = g(vp + "embeddings.class_embedding")
         self.pos = g(vp + "embeddings.position_embedding.weight")
         assert self.pos.shape == (a.tokens, a.hidden_size), f"position table {tuple(self.pos.shape)} does not match the config"
         self.pre_ln_w, self.pre_ln_b = g(vp + "pre_layrnorm.weight"), g(vp + "pre_layrnorm.bias")
-        self.layers = []
-        for i in range(a.num_hidden_layers):
-            p = f"{vp}encoder.layers.{i}."
-            cat = lambda suf: torch.cat([g(p + f"self_attn.{n}_proj.{suf}") for n in ("q", "k", "v")]).contiguous()
-            self.layers.append(_VitLayer(g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias"), cat("weight"), cat("bias"),
-                                         g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"),
-                                         g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias"),
-                                         g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")))
+        self.layers = load_encoder_layers(g, vp + "encoder.layers.", a.num_hidden_layers)
         self.post_ln_w, self.post_ln_b = g(vp + "post_layernorm.weight"), g(vp + "post_layernorm.bias")
         self.proj_w = g("visual_projection.weight")
         assert self.proj_w.shape == (a.projection_dim, a.hidden_size)
@@ -82,20 +75,9 @@ class ClipVisionEngine:
         del cols, patches
         if hidden_states is not None:
             hidden_states.append(x.view(n, T, E).clone())
+        attend = dense_attend(n, T, nh, hd)
         for L in self.layers:
-            y = ops.layernorm(x, L.ln1_w, L.ln1_b, a.layer_norm_eps)
-            qkv = ops.linear(y, L.qkv_w, bias=L.qkv_b)
-            o = ops.attention(qkv, qkv.view(-1)[E:], qkv.view(-1)[2 * E:], n, T, T, nh, nh, hd,
-                              T * 3 * E, 3 * E, T * 3 * E, 3 * E, hd ** -0.5, 0)
-            del qkv
-            ops.linear(o.view(n * T, E), L.out_w, bias=L.out_b, residual=x, out=x)
-            y = ops.layernorm(x, L.ln2_w, L.ln2_b, a.layer_norm_eps)
-            if a.hidden_act == "quick_gelu":
-                y = ops.quick_gelu_(ops.linear(y, L.fc1_w, bias=L.fc1_b))
-            else:
-                y = ops.linear(y, L.fc1_w, bias=L.fc1_b, act="gelu")
-            ops.linear(y, L.fc2_w, bias=L.fc2_b, residual=x, out=x)
-            del y, o
+            encoder_layer_(x, L, a.layer_norm_eps, a.hidden_act, attend)
             if hidden_states is not None:
                 hidden_states.append(x.view(n, T, E).clone())
         # pooled = post_layernorm(last_hidden_state[:, 0]): a LayerNorm over row 0 of every T rows
@@ -180,20 +162,13 @@ class ClipTextEngine:
             raise RuntimeError("ClipTextEngine runs on the GPU only (liblicv_hip has no CPU fallback)")
         sd = clip_text_state(state_dict)
         self.arch, self.device = a, dev
-        g = lambda k: _bf(sd[k], dev)
+        g = lambda k: bf16_on(sd[k], dev)
         tp = "text_model."
         self.tok = g(tp + "embeddings.token_embedding.weight")
         self.pos = g(tp + "embeddings.position_embedding.weight")
         assert self.tok.shape == (a.vocab_size, a.hidden_size), f"token table {tuple(self.tok.shape)} does not match the config"
         assert self.pos.shape == (a.max_position_embeddings, a.hidden_size), f"position table {tuple(self.pos.shape)} does not match the config"
-        self.layers = []
-        for i in range(a.num_hidden_layers):
-            p = f"{tp}encoder.layers.{i}."
-            cat = lambda suf: torch.cat([g(p + f"self_attn.{n}_proj.{suf}") for n in ("q", "k", "v")]).contiguous()
-            self.layers.append(_VitLayer(g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias"), cat("weight"), cat("bias"),
-                                         g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"),
-                                         g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias"),
-                                         g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")))
+        self.layers = load_encoder_layers(g, tp + "encoder.layers.", a.num_hidden_layers)
         self.final_ln_w, self.final_ln_b = g(tp + "final_layer_norm.weight"), g(tp + "final_layer_norm.bias")
         self.proj_w = g("text_projection.weight")
         assert self.proj_w.shape == (a.projection_dim, a.hidden_size)
@@ -211,19 +186,9 @@ class ClipTextEngine:
         total = x.shape[0]
         if hidden_states is not None:
             hidden_states.append(x.clone())
+        attend = lambda qkv: ops.attn_varlen_causal(qkv, pk.cu_seqlens, cu_dev, nh, hd, hd ** -0.5)
         for L in self.layers:
-            y = ops.layernorm(x, L.ln1_w, L.ln1_b, a.layer_norm_eps)
-            qkv = ops.linear(y, L.qkv_w, bias=L.qkv_b)
-            o = ops.attn_varlen_causal(qkv, pk.cu_seqlens, cu_dev, nh, hd, hd ** -0.5)
-            del qkv
-            ops.linear(o, L.out_w, bias=L.out_b, residual=x, out=x)
-            y = ops.layernorm(x, L.ln2_w, L.ln2_b, a.layer_norm_eps)
-            if a.hidden_act == "quick_gelu":
-                y = ops.quick_gelu_(ops.linear(y, L.fc1_w, bias=L.fc1_b))
-            else:
-                y = ops.linear(y, L.fc1_w, bias=L.fc1_b, act="gelu")
-            ops.linear(y, L.fc2_w, bias=L.fc2_b, residual=x, out=x)
-            del y, o
+            encoder_layer_(x, L, a.layer_norm_eps, a.hidden_act, attend)
             if hidden_states is not None:
                 hidden_states.append(x.clone())
         assert x.shape == (total, E)

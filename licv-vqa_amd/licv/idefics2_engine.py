@@ -20,16 +20,10 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import frontend, ops
+from .blocks import (FOLD_MIN_ROWS, EncoderLayer, bf16_on, causal_self_attention, dense_attend, encoder_layer_, hook_args,
+                     load_encoder_layers, lm_logits, pad_cols, rotary_tables, run_slices)
 from .config import Idefics2Arch
-from .idefics_engine import KVCache, _bf, _pad_cols
-
-
-@dataclass
-class _SigLayer:
-    ln1_w: torch.Tensor; ln1_b: torch.Tensor; qkv_w: torch.Tensor; qkv_b: torch.Tensor
-    out_w: torch.Tensor; out_b: torch.Tensor; ln2_w: torch.Tensor; ln2_b: torch.Tensor
-    fc1_w: torch.Tensor; fc1_b: torch.Tensor; fc2_w: torch.Tensor; fc2_b: torch.Tensor
-    q8: Optional[dict] = None           # fp8 copies of the four projection weights when fp8_vision
+from .idefics_engine import KVCache
 
 
 @dataclass
@@ -56,31 +50,16 @@ class Idefics2Weights:
         projections of every SigLIP layer."""
         a, dev = arch, torch.device(device)
         self.arch, self.device, self.fp8_text, self.fp8_vision = arch, dev, fp8_text, fp8_vision
-        g = lambda k: _bf(sd[k], dev)
+        g = lambda k: bf16_on(sd[k], dev)
         cat = lambda p, names, suf: torch.cat([g(p + f"{n}.{suf}") for n in names]).contiguous()
         vp = "model.vision_model."
         self.patch_ld = (3 * a.v_patch * a.v_patch + 63) // 64 * 64
-        self.patch_w = _pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
+        self.patch_w = pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
         self.patch_b = g(vp + "embeddings.patch_embedding.bias")
         self.pos = g(vp + "embeddings.position_embedding.weight")
-        self.vit: List[_SigLayer] = []
         # MLP width padded to a multiple of 64 (4304 -> 4352) with zero rows / bias / columns: gelu(0) = 0, so the result
         # is unchanged and fc2's K dimension qualifies for the 256x256 LDS-DMA GEMM (K % 64 == 0)
-        ipad = (a.v_inter + 63) // 64 * 64
-
-        def pad_rows(t):
-            out = torch.zeros((ipad, *t.shape[1:]), dtype=t.dtype, device=t.device)
-            out[: t.shape[0]] = t
-            return out
-        for i in range(a.v_layers):
-            p = f"{vp}encoder.layers.{i}."
-            qkv = ("q_proj", "k_proj", "v_proj")
-            self.vit.append(_SigLayer(g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias"),
-                                      cat(p + "self_attn.", qkv, "weight"), cat(p + "self_attn.", qkv, "bias"),
-                                      g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"),
-                                      g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias"),
-                                      pad_rows(g(p + "mlp.fc1.weight")), pad_rows(g(p + "mlp.fc1.bias")),
-                                      _pad_cols(g(p + "mlp.fc2.weight"), ipad), g(p + "mlp.fc2.bias")))
+        self.vit: List[EncoderLayer] = load_encoder_layers(g, vp + "encoder.layers.", a.v_layers, pad_inter=(a.v_inter + 63) // 64 * 64)
         if fp8_vision:
             for L in self.vit:
                 L.q8 = {n: ops.quantize_fp8(getattr(L, n)) for n in ("qkv_w", "out_w", "fc1_w", "fc2_w")}
@@ -115,11 +94,7 @@ class Idefics2Weights:
                 L.q8 = {n: ops.quantize_fp8(getattr(L, n)) for n in ("qkv_w", "o_w", "gu_w", "down_w") if ok(getattr(L, n))}
         self.final_ln = g(tp + "norm.weight")
         self.lm_head = g("lm_head.weight")
-        # rotary tables: fp32 inv_freq and angles, cast to the model dtype (hf:mistral/modeling_mistral.py MistralRotaryEmbedding)
-        hd = a.head_dim
-        inv = 1.0 / (a.rope_base ** (torch.arange(0, hd, 2, dtype=torch.float) / hd))
-        emb = torch.cat((torch.outer(torch.arange(max_positions, dtype=torch.float), inv),) * 2, dim=-1)
-        self.cos, self.sin = _bf(emb.cos(), dev), _bf(emb.sin(), dev)
+        self.cos, self.sin = rotary_tables(a.head_dim, a.rope_base, max_positions, dev)
         self.max_positions = max_positions
 
 
@@ -212,25 +187,12 @@ class Idefics2Engine:
         return e[3]
 
     def _forward_slices(self, parts: int, input_ids, attention_mask, pixel_values, pixel_attention_mask, position_ids, **kw):
-        dev = self.w.device
         B = input_ids.shape[0]
-        cur = torch.cuda.current_stream(dev)
-        while len(self._side_streams) < parts:
-            self._side_streams.append(torch.cuda.Stream(device=dev))
         cut = tuple(B * i // parts for i in range(parts + 1))
         ids, am, pv = self._views(input_ids, cut), self._views(attention_mask, cut), self._views(pixel_values, cut)
         pam, pos = self._views(pixel_attention_mask, cut), self._views(position_ids, cut)
-        outs = []
-        for i in range(parts):
-            st = self._side_streams[i]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                outs.append(self._forward_one(ids[i], am[i], pv[i], pam[i], position_ids=pos[i], **kw))
-        for i in range(parts):
-            cur.wait_stream(self._side_streams[i])
-        for o in outs:
-            o.record_stream(cur)
-        return torch.cat(outs, 0)
+        run = lambda i: self._forward_one(ids[i], am[i], pv[i], pam[i], position_ids=pos[i], **kw)
+        return torch.cat(run_slices(self._side_streams, self.w.device, parts, run), 0)
 
     # ----------------------------------------------------------------------------------- vision + connector
     def encode_images(self, pixel_values: torch.Tensor, pixel_attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -258,31 +220,16 @@ class Idefics2Engine:
         all_valid = n_valid == n * T
         pos_ids = pos_ids.reshape(-1)
 
-        E, nh, hd = a.v_hidden, a.v_heads, a.v_head_dim
+        nh, hd = a.v_heads, a.v_head_dim
         cols = ops.im2col_patches(pv, P, w.patch_ld)
         pos_rows = ops.embed_gather(pos_ids, w.pos, None, w.pos.shape[0])
         x = ops.linear(cols, w.patch_w, bias=w.patch_b, residual=pos_rows)
         del cols, pos_rows
         act = "gelu_tanh" if a.v_act == "gelu_pytorch_tanh" else "gelu"
-        mode, kvld = (0, None) if all_valid else (2, valid)
-        fp8v = w.fp8_vision and n * T >= 512            # e4m3 operands: the LayerNorms write the fp8 rows themselves, no bf16 copy
+        attend = dense_attend(n, T, nh, hd) if all_valid else dense_attend(n, T, nh, hd, 2, valid)
+        fp8v = w.fp8_vision and n * T >= FOLD_MIN_ROWS        # e4m3 operands for the tower's projections
         for L in w.vit:
-            if fp8v:
-                qkv = ops.linear_fp8(*ops.layernorm_q8(x, L.ln1_w, L.ln1_b, a.v_ln_eps), *L.q8["qkv_w"], bias=L.qkv_b)
-            else:
-                qkv = ops.linear(ops.layernorm(x, L.ln1_w, L.ln1_b, a.v_ln_eps), L.qkv_w, bias=L.qkv_b)
-            o = ops.attention(qkv, qkv.view(-1)[E:], qkv.view(-1)[2 * E:], n, T, T, nh, nh, hd, T * 3 * E, 3 * E, T * 3 * E, 3 * E,
-                              hd ** -0.5, mode, key_valid=kvld)
-            del qkv
-            if fp8v:
-                ops.linear_fp8(*ops.quantize_fp8(o.view(n * T, E)), *L.q8["out_w"], bias=L.out_b, residual=x, out=x)
-                y = ops.linear_fp8(*ops.layernorm_q8(x, L.ln2_w, L.ln2_b, a.v_ln_eps), *L.q8["fc1_w"], bias=L.fc1_b, act=act)
-                ops.linear_fp8(*ops.quantize_fp8(y), *L.q8["fc2_w"], bias=L.fc2_b, residual=x, out=x)
-            else:
-                ops.linear(o.view(n * T, E), L.out_w, bias=L.out_b, residual=x, out=x)
-                y = ops.linear(ops.layernorm(x, L.ln2_w, L.ln2_b, a.v_ln_eps), L.fc1_w, bias=L.fc1_b, act=act)
-                ops.linear(y, L.fc2_w, bias=L.fc2_b, residual=x, out=x)
-            del y, o
+            encoder_layer_(x, L, a.v_ln_eps, act, attend, fp8=fp8v)
         x = ops.layernorm(x, w.post_ln_w, w.post_ln_b, a.v_ln_eps)
         return self._connector(x, valid, n, T)
 
@@ -316,7 +263,7 @@ class Idefics2Engine:
         """A text-stack projection: fp8 operands when the layer carries fp8 weights and the GEMM is large, else bf16."""
         if isinstance(x, tuple):                         # rows already in e4m3 (written by the norm kernel that produced them)
             return ops.linear_fp8(x[0], x[1], *L.q8[name], **kw)
-        if L.q8 is not None and name in L.q8 and x.shape[0] >= 512:
+        if L.q8 is not None and name in L.q8 and x.shape[0] >= FOLD_MIN_ROWS:
             xq, xs = ops.quantize_fp8(x)
             wq, ws = L.q8[name]
             return ops.linear_fp8(xq, xs, wq, ws, **kw)
@@ -325,7 +272,7 @@ class Idefics2Engine:
     @staticmethod
     def _q8_in(L: _TextLayer, name: str, M: int) -> bool:
         """Does projection `name` of this layer take e4m3 rows (then its producer writes them, see ops.*_q8)?"""
-        return L.q8 is not None and name in L.q8 and M >= 512
+        return L.q8 is not None and name in L.q8 and M >= FOLD_MIN_ROWS
 
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 pixel_values: Optional[torch.Tensor] = None, pixel_attention_mask: Optional[torch.Tensor] = None,
@@ -380,13 +327,9 @@ class Idefics2Engine:
         else:
             pos = position_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
             assert pos.numel() == M
-        idx_of = {int(l): i for i, l in enumerate(hook_layers)} if (icv is not None and hook_layers is not None) else {}
-        if icv is not None:
-            icv = icv.to(device=dev, dtype=torch.float32).contiguous()
-            if alpha is not None:
-                alpha = alpha.to(device=dev, dtype=torch.float32).contiguous()
-        qd, kd = nh * hd, nkv * hd
-        ldq = qd + 2 * kd
+        idx_of, icv, alpha = hook_args(icv, alpha, hook_layers, dev)
+        qd = nh * hd
+        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past)
         xn = None
         for l, L in enumerate(w.text):
             if xn is not None:
@@ -396,25 +339,10 @@ class Idefics2Engine:
             else:
                 x = ops.rmsnorm(h, L.in_ln, a.rms_eps, 1)
             xn = None
-            if kv_cache is not None and S == 1:                       # a decode step: rotary + append + GQA attention in one launch
-                qs = ops.linear_produce(x, L.qkv_w) if not isinstance(x, tuple) else None
-                o = ops.decode_attn(qs if qs is not None else self._tlin(x, L, "qkv_w"), w.cos, w.sin, pos, kv_cache.kv[l], past, nh, nkv, hd,
-                                    hd ** -0.5, key_valid=key_valid, kv_rows=kv_cache.rows)
-                qkv = None
-            else:
-                qkv = self._tlin(x, L, "qkv_w")
-                ops.rotary_(qkv, w.cos, w.sin, pos, M, nh + nkv, hd, ldq, 0, 1)   # Q heads | K heads are contiguous in the fused row: one launch
-            if qkv is None:
-                pass
-            elif kv_cache is None:
-                o = ops.attention(qkv, qkv.view(-1)[qd:], qkv.view(-1)[qd + kd:], B, S, S, nh, nkv, hd, S * ldq, ldq, S * ldq, ldq,
-                                  hd ** -0.5, 1, key_valid=key_valid)
-            else:
-                cache = kv_cache.kv[l]
-                cache[:, past:Sk] = qkv.view(B, S, ldq)[:, :, qd:]                         # append K|V (device copy)
-                o = ops.attention(qkv, cache, cache.view(-1)[kd:], B, S, Sk, nh, nkv, hd, S * ldq, ldq, kv_cache.max_len * 2 * kd, 2 * kd,
-                                  hd ** -0.5, 1, key_valid=key_valid)
-            if M >= 512 and cap is None and self.fold_residual:   # the residual add folded into the norm that follows (as in IdeficsEngine): bit-identical
+            # Q heads | K heads are contiguous in the fused row: one rotary launch over nh + nkv heads
+            o, qkv = causal_self_attention(lambda: self._tlin(x, L, "qkv_w"), x, L.qkv_w, w.cos, w.sin, pos, key_valid, B, S, nh, nkv, hd,
+                                           (nh + nkv, 0, 1), **cached(l))
+            if M >= FOLD_MIN_ROWS and cap is None and self.fold_residual:   # the residual add folded into the norm that follows (as in IdeficsEngine): bit-identical
                 if self._q8_in(L, "gu_w", M):
                     x = ops.add_rmsnorm_q8_(h, self._tlin(o.view(M, qd), L, "o_w"), L.post_ln, a.rms_eps, 1)
                 else:
@@ -451,8 +379,4 @@ class Idefics2Engine:
         x = xn if xn is not None else ops.rmsnorm(h, w.final_ln, a.rms_eps, 1)
         if capture is not None:
             capture["image_hidden_states"] = image_hidden_states
-        if logits_rows is not None:
-            return ops.linear(x.index_select(0, logits_rows), w.lm_head)
-        logits = ops.linear(x, w.lm_head)
-        V = logits.shape[-1]
-        return logits.view(B, S, V) if logits.is_contiguous() else logits.as_strided((B, S, V), (S * logits.stride(0), logits.stride(0), 1))
+        return lm_logits(x, w.lm_head, B, S, logits_rows)

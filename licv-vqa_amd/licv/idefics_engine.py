@@ -15,33 +15,15 @@ Data layout in HBM (all row-major, tokens flattened to M = B*S rows):
 """
 from __future__ import annotations
 
-import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from . import ops
+from .blocks import (FOLD_MIN_ROWS, EncoderLayer, bf16_on, causal_self_attention, dense_attend, encoder_layer_, hook_args,
+                     load_encoder_layers, lm_logits, pad_cols, rotary_tables, run_slices)
 from .config import IdeficsArch
-
-
-def _bf(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.detach().to(device=dev, dtype=torch.bfloat16).contiguous()
-
-
-def _pad_cols(w: torch.Tensor, to: int) -> torch.Tensor:
-    if w.shape[1] == to:
-        return w.contiguous()
-    out = torch.zeros((w.shape[0], to), dtype=w.dtype, device=w.device)
-    out[:, : w.shape[1]] = w
-    return out
-
-
-@dataclass
-class _VitLayer:
-    ln1_w: torch.Tensor; ln1_b: torch.Tensor; qkv_w: torch.Tensor; qkv_b: torch.Tensor
-    out_w: torch.Tensor; out_b: torch.Tensor; ln2_w: torch.Tensor; ln2_b: torch.Tensor
-    fc1_w: torch.Tensor; fc1_b: torch.Tensor; fc2_w: torch.Tensor; fc2_b: torch.Tensor
 
 
 @dataclass
@@ -72,24 +54,17 @@ class IdeficsWeights:
     def __init__(self, sd: Dict[str, torch.Tensor], arch: IdeficsArch, device="cuda"):
         a, dev = arch, torch.device(device)
         self.arch, self.device = arch, dev
-        g = lambda k: _bf(sd[k], dev)
+        g = lambda k: bf16_on(sd[k], dev)
         self.embed = g("model.embed_tokens.weight")
         self.embed_extra = g("model.embed_tokens.additional_embedding.weight") if a.additional_vocab_size else None
         vp = "model.vision_model."
         kdim = 3 * a.v_patch * a.v_patch
         self.patch_ld = (kdim + 63) // 64 * 64
-        self.patch_w = _pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
+        self.patch_w = pad_cols(g(vp + "embeddings.patch_embedding.weight").flatten(1), self.patch_ld)
         self.cls = g(vp + "embeddings.class_embedding")
         self.pos = g(vp + "embeddings.position_embedding.weight")
         self.pre_ln_w, self.pre_ln_b = g(vp + "pre_layrnorm.weight"), g(vp + "pre_layrnorm.bias")
-        self.vit: List[_VitLayer] = []
-        for i in range(a.v_layers):
-            p = f"{vp}encoder.layers.{i}."
-            cat = lambda suf: torch.cat([g(p + f"self_attn.{n}_proj.{suf}") for n in ("q", "k", "v")]).contiguous()
-            self.vit.append(_VitLayer(g(p + "layer_norm1.weight"), g(p + "layer_norm1.bias"), cat("weight"), cat("bias"),
-                                      g(p + "self_attn.out_proj.weight"), g(p + "self_attn.out_proj.bias"),
-                                      g(p + "layer_norm2.weight"), g(p + "layer_norm2.bias"),
-                                      g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g(p + "mlp.fc2.weight"), g(p + "mlp.fc2.bias")))
+        self.vit: List[EncoderLayer] = load_encoder_layers(g, vp + "encoder.layers.", a.v_layers)
         self.perc: List[_PercBlock] = []
         if a.use_resampler:
             rp = "model.perceiver_resampler."
@@ -131,11 +106,7 @@ class IdeficsWeights:
         if a.additional_vocab_size:
             head = torch.cat([head, g("lm_head.additional_fc.weight")]).contiguous()
         self.lm_head = head
-        # rotary tables exactly as hf:idefics/modeling_idefics.py:357-379 builds them (fp32 maths, cast to bf16)
-        inv = 1.0 / (a.rope_base ** (torch.arange(0, a.head_dim, 2, dtype=torch.int64).to(torch.float) / a.head_dim))
-        t = torch.arange(a.max_positions, dtype=torch.int64).to(torch.float)
-        emb = torch.cat((torch.outer(t, inv),) * 2, dim=-1)
-        self.cos, self.sin = _bf(emb.cos(), dev), _bf(emb.sin(), dev)
+        self.cos, self.sin = rotary_tables(a.head_dim, a.rope_base, a.max_positions, dev)
 
 
 class KVCache:
@@ -196,7 +167,6 @@ class IdeficsEngine:
                         logits_rows=None, **kw):
         dev = self.w.device
         B, S = input_ids.shape
-        cur = torch.cuda.current_stream(dev)
         cut = [B * i // parts for i in range(parts + 1)]
         rows_of = [None] * parts
         if logits_rows is not None:
@@ -209,24 +179,13 @@ class IdeficsEngine:
                 return self._forward_one(input_ids, attention_mask, pixel_values, image_attention_mask, image_states,
                                          logits_rows=logits_rows, **kw)
             rows_of = [(r[info[i]:info[i + 1]] - cut[i] * S).contiguous() for i in range(parts)]
-        while len(self._side_streams) < parts:
-            self._side_streams.append(torch.cuda.Stream(device=dev))
-        outs = []
-        for i in range(parts):
-            if logits_rows is not None and rows_of[i].numel() == 0:
-                continue
-            st = self._side_streams[i]
-            st.wait_stream(cur)                                       # the inputs were produced on the caller's stream
-            sl = slice(cut[i], cut[i + 1])
-            with torch.cuda.stream(st):
-                outs.append(self._forward_one(input_ids[sl], None if attention_mask is None else attention_mask[sl],
-                                              None if pixel_values is None else pixel_values[sl], image_attention_mask[sl],
-                                              None if image_states is None else image_states[sl], logits_rows=rows_of[i], **kw))
-        for i in range(parts):
-            cur.wait_stream(self._side_streams[i])
-        for o in outs:
-            o.record_stream(cur)                                      # allocated on a side stream, read on the caller's from here on
-        return torch.cat(outs, 0)
+
+        def run(i):
+            sl = lambda t: None if t is None else t[cut[i]:cut[i + 1]]
+            return self._forward_one(sl(input_ids), sl(attention_mask), sl(pixel_values), sl(image_attention_mask), sl(image_states),
+                                     logits_rows=rows_of[i], **kw)
+        empty = [i for i in range(parts) if logits_rows is not None and rows_of[i].numel() == 0]
+        return torch.cat(run_slices(self._side_streams, dev, parts, run, skip=empty), 0)
 
     # ----------------------------------------------------------------------------------- vision side
     def encode_images(self, pixel_values: torch.Tensor) -> torch.Tensor:
@@ -244,17 +203,9 @@ class IdeficsEngine:
         x = ops.vit_embed_ln(patches, w.cls, w.pos, w.pre_ln_w, w.pre_ln_b, n_img, T - 1, a.v_ln_eps).view(n_img * T, E)
         del patches
         act = "gelu" if a.v_act == "gelu" else "gelu_tanh"
+        attend = dense_attend(n_img, T, nh, hd)
         for L in w.vit:
-            y = ops.layernorm(x, L.ln1_w, L.ln1_b, a.v_ln_eps)
-            qkv = ops.linear(y, L.qkv_w, bias=L.qkv_b)
-            o = ops.attention(qkv, qkv.view(-1)[E:], qkv.view(-1)[2 * E:], n_img, T, T, nh, nh, hd,
-                              T * 3 * E, 3 * E, T * 3 * E, 3 * E, hd ** -0.5, 0)
-            del qkv
-            ops.linear(o.view(n_img * T, E), L.out_w, bias=L.out_b, residual=x, out=x)
-            y = ops.layernorm(x, L.ln2_w, L.ln2_b, a.v_ln_eps)
-            y = ops.linear(y, L.fc1_w, bias=L.fc1_b, act=act)
-            ops.linear(y, L.fc2_w, bias=L.fc2_b, residual=x, out=x)
-            del y, o
+            encoder_layer_(x, L, a.v_ln_eps, act, attend)
         if not a.use_resampler:
             return x.view(B, N * T, E)
         return self._perceiver(x, n_img).view(B, N * a.r_latents, E)
@@ -324,16 +275,11 @@ class IdeficsEngine:
         Nk = image_states.shape[1]
         E = image_states.shape[2]
         img_len = a.image_seq_len
-        n_img = Nk // img_len
         img_mask = image_attention_mask.to(torch.int32).contiguous()
         gate = (img_mask != 0).any(-1).to(torch.float32).reshape(-1).contiguous()      # cross_attention_gate
         key_valid = attention_mask.to(torch.int32).contiguous()
         pos = self._position_ids(attention_mask, S).reshape(-1)
-        idx_of = {int(l): i for i, l in enumerate(hook_layers)} if (icv is not None and hook_layers is not None) else {}
-        if icv is not None:
-            icv = icv.to(device=dev, dtype=torch.float32).contiguous()
-            if alpha is not None:
-                alpha = alpha.to(device=dev, dtype=torch.float32).contiguous()
+        idx_of, icv, alpha = hook_args(icv, alpha, hook_layers, dev)
 
         past = kv_cache.len if kv_cache is not None else 0
         assert past + S == Sk, "attention_mask must span past + new tokens"
@@ -357,7 +303,8 @@ class IdeficsEngine:
                 return w.xat[(l + 1) // a.cross_layer_interval].in_ln
             return w.dec[l + 1].in_ln
 
-        foldable = M >= 512 and capture is None and save_hook_inputs is None and self.fuse_hook_norm
+        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past)
+        foldable = M >= FOLD_MIN_ROWS and capture is None and save_hook_inputs is None and self.fuse_hook_norm
         pending = None                               # a cross layer's MLP branch (and its gate scale) waiting for the next norm to add it
         for l in range(a.num_layers):
             if l % a.cross_layer_interval == 0:
@@ -388,23 +335,8 @@ class IdeficsEngine:
             else:
                 x = xn if xn is not None else ops.rmsnorm(h, D.in_ln, a.rms_eps)
             xn = None
-            if kv_cache is None:
-                qkv = ops.linear(x, D.qkv_w)
-                ops.rotary_(qkv, w.cos, w.sin, pos, M, nh, hd, 3 * H, H, 2)
-                o = ops.attention(qkv, qkv.view(-1)[H:], qkv.view(-1)[2 * H:], B, S, S, nh, nh, hd, S * 3 * H, 3 * H,
-                                  S * 3 * H, 3 * H, hd ** -0.5, 1, key_valid=key_valid)
-            elif S == 1:                                                 # a decode step: rotary + append + attention in one launch
-                qkv = None
-                qs = ops.linear_produce(x, D.qkv_w)
-                o = ops.decode_attn(qs if qs is not None else ops.linear(x, D.qkv_w), w.cos, w.sin, pos, kv_cache.kv[l], past, nh, nh, hd,
-                                    hd ** -0.5, key_valid=key_valid, kv_rows=kv_cache.rows)
-            else:
-                qkv = ops.linear(x, D.qkv_w)
-                ops.rotary_(qkv, w.cos, w.sin, pos, M, nh, hd, 3 * H, H, 2)
-                cache = kv_cache.kv[l]
-                cache[:, past:past + S] = qkv.view(B, S, 3 * H)[:, :, H:]          # append K|V (device copy)
-                o = ops.attention(qkv, cache, cache.view(-1)[H:], B, S, Sk, nh, nh, hd, S * 3 * H, 3 * H,
-                                  kv_cache.max_len * 2 * H, 2 * H, hd ** -0.5, 1, key_valid=key_valid)
+            o, qkv = causal_self_attention(lambda: ops.linear(x, D.qkv_w), x, D.qkv_w, w.cos, w.sin, pos, key_valid, B, S, nh, nh, hd,
+                                           (nh, H, 2), **cached(l))
             # Large batches (the 256-tile GEMMs), nothing captured: the layer's two residual adds leave the GEMM epilogues (a
             # read-modify-write of the fp32 stream costs the o / down projections 16-28 %) and are folded into the row kernels that
             # follow — same sums, same rounding points, bit-identical — so both projections take the register-direct epilogue
@@ -447,9 +379,4 @@ class IdeficsEngine:
         if capture is not None:
             capture["final_norm"] = x.view(B, S, H).clone()
             capture["image_states"] = image_states
-        if logits_rows is not None:
-            x = x.index_select(0, logits_rows)
-            return ops.linear(x, w.lm_head)
-        logits = ops.linear(x, w.lm_head)
-        return logits.view(B, S, logits.shape[-1]) if logits.is_contiguous() else \
-            logits.as_strided((B, S, logits.shape[-1]), (S * logits.stride(0), logits.stride(0), 1))
+        return lm_logits(x, w.lm_head, B, S, logits_rows)

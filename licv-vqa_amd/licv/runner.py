@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .blocks import logits_view
 
 P, I64, F = C.c_void_p, C.c_int64, C.c_float
 
@@ -139,6 +140,4 @@ class TextRunner:
         if kv_cache is not None:
             kv_cache.len += S
         out = logits if ldc == V else logits[:, :V]
-        if logits_rows is not None:
-            return out
-        return out.view(B, S, V) if out.is_contiguous() else out.as_strided((B, S, V), (S * ldc, ldc, 1))
+        return out if logits_rows is not None else logits_view(out, B, S)

@@ -12,11 +12,12 @@ MFMA GEMM on transposed weight copies (built once by ``TrainWeights``).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
 from . import ops
+from .blocks import causal_self_attention, hook_args, lm_logits
 from .idefics_engine import IdeficsEngine, IdeficsWeights
 
 
@@ -32,25 +33,49 @@ def _unpack_gate_up(packed: torch.Tensor) -> torch.Tensor:
     return torch.cat([blk[:, 0].reshape(two_i // 2, K), blk[:, 1].reshape(two_i // 2, K)]).contiguous()
 
 
-class TrainWeights:
-    """Transposed / unfused copies of the language-stack weights needed by the backward (built lazily, once)."""
+def _transposed(L, names) -> dict:
+    """The backward's copies of one layer: the unfused (2I, H) gate | up rows recovered from the engine's packed buffer (bit-identical
+    rows), their transpose, and `name`_T for every projection `name`_w in `names`."""
+    gu = _unpack_gate_up(L.gu_w)
+    return dict(gu=gu, gu_T=_t(gu), **{n + "_T": _t(getattr(L, n + "_w")) for n in names})
 
-    def __init__(self, w: IdeficsWeights, sd: Optional[Dict[str, torch.Tensor]] = None):
-        """``sd`` (the HF-named state dict) is optional: without it the unfused gate|up copy is recovered from the engine's
-        packed buffer (bit-identical rows)."""
-        dev = w.device
-        self.dec, self.xat = [], []
-        for i, D in enumerate(w.dec):
-            gu = _unpack_gate_up(D.gu_w)                                                                 # (2I, H) gate | up
-            self.dec.append(dict(gu=gu, gu_T=_t(gu), down_T=_t(D.down_w), o_T=_t(D.o_w), qkv_T=_t(D.qkv_w)))
-        for j, X in enumerate(w.xat):
-            gu = _unpack_gate_up(X.gu_w)
-            self.xat.append(dict(gu=gu, gu_T=_t(gu), down_T=_t(X.down_w), o_T=_t(X.o_w), q_T=_t(X.q_w)))
-        V = w.lm_head.shape[0]
-        head_T = torch.zeros((w.lm_head.shape[1], (V + 7) // 8 * 8), dtype=torch.bfloat16, device=dev)     # (H, V padded to 8)
-        head_T[:, :V] = w.lm_head.t()
-        self.head_T = head_T
-        self.neg_sin = (-w.sin.float()).to(torch.bfloat16).contiguous()
+
+def _head_T(w) -> torch.Tensor:
+    V = w.lm_head.shape[0]
+    head_T = torch.zeros((w.lm_head.shape[1], (V + 7) // 8 * 8), dtype=torch.bfloat16, device=w.device)   # (H, V padded to 8)
+    head_T[:, :V] = w.lm_head.t()
+    return head_T
+
+
+def _neg_sin(w) -> torch.Tensor:
+    return (-w.sin.float()).to(torch.bfloat16).contiguous()
+
+
+def _head_backward(st: dict, dlogits_rows: torch.Tensor, w, tw, M: int, H: int, eps: float, flavour: int) -> torch.Tensor:
+    """Head + final norm: the (R, V padded) bf16 grad of the selected logit rows -> d loss / d h_final, (M, H) fp32."""
+    assert dlogits_rows.shape[1] == tw.head_T.shape[1] and dlogits_rows.is_contiguous(), "pass the padded grad from ops.kl_rows_bwd"
+    d_xf = torch.zeros((M, H), dtype=torch.bfloat16, device=w.device)
+    d_xf.index_copy_(0, st["logits_rows"], ops.linear(dlogits_rows, tw.head_T))
+    dh = torch.empty((M, H), dtype=torch.float32, device=w.device)
+    ops.rmsnorm_bwd(st["h_final"], w.final_ln, d_xf, dh, eps, accumulate=False, flavour=flavour)
+    return dh
+
+
+def _mlp_backward(d_branch: torch.Tensor, gu: torch.Tensor, h_mid: torch.Tensor, post_ln: torch.Tensor, T: dict, dh: torch.Tensor,
+                  eps: float, flavour: int, scale: Optional[float] = None) -> None:
+    """dh += the gradient that the MLP branch (post norm -> gate | up -> SwiGLU -> down [x scale]) passes to its input h_mid, from the
+    gradient d_branch of the branch's output."""
+    d_act = ops.linear(ops.branch_grad(d_branch, scale=scale), T["down_T"])
+    ops.rmsnorm_bwd_from(h_mid, post_ln, ops.swiglu_bwd(gu, d_act), T["gu_T"], dh, eps, accumulate=True, flavour=flavour)
+
+
+class TrainWeights:
+    """Transposed / unfused copies of the language-stack weights needed by the backward (built once)."""
+
+    def __init__(self, w: IdeficsWeights):
+        self.dec = [_transposed(D, ("down", "o", "qkv")) for D in w.dec]
+        self.xat = [_transposed(X, ("down", "o", "q")) for X in w.xat]
+        self.head_T, self.neg_sin = _head_T(w), _neg_sin(w)
 
 
 class StudentPass:
@@ -79,9 +104,7 @@ class StudentPass:
         gate = (img_mask != 0).any(-1).to(torch.float32).reshape(-1).contiguous()
         key_valid = attention_mask.to(torch.int32).contiguous()
         pos = e._position_ids(attention_mask, S).reshape(-1)
-        idx_of = {int(l): i for i, l in enumerate(hook_layers)}
-        icv = icv.detach().to(device=dev, dtype=torch.float32).contiguous()
-        alpha = alpha.detach().to(device=dev, dtype=torch.float32).contiguous() if alpha is not None else None
+        idx_of, icv, alpha = hook_args(icv, alpha, hook_layers, dev)
         img2d = image_states.reshape(B * Nk, E)
 
         st = dict(B=B, S=S, Nk=Nk, img_len=img_len, img_mask=img_mask, gate=gate, key_valid=key_valid, pos=pos, icv=icv, alpha=alpha,
@@ -114,11 +137,8 @@ class StudentPass:
             D, T = w.dec[l], tw.dec[l]
             rec["h_in"] = h
             xn = ops.rmsnorm(h, D.in_ln, a.rms_eps)
-            qkv = ops.linear(xn, D.qkv_w)
-            ops.rotary_(qkv, w.cos, w.sin, pos, M, nh, hd, 3 * H, H, 2)
-            rec["qkv"] = qkv
-            o = ops.attention(qkv, qkv.view(-1)[H:], qkv.view(-1)[2 * H:], B, S, S, nh, nh, hd, S * 3 * H, 3 * H, S * 3 * H, 3 * H,
-                              hd ** -0.5, 1, key_valid=key_valid)
+            o, rec["qkv"] = causal_self_attention(lambda: ops.linear(xn, D.qkv_w), xn, D.qkv_w, w.cos, w.sin, pos, key_valid, B, S,
+                                                  nh, nh, hd, (nh, H, 2))
             h = ops.linear(o.view(M, H), D.o_w, residual=h)
             rec["h_mid"] = h
             xn = ops.rmsnorm(h, D.post_ln, a.rms_eps)
@@ -133,28 +153,18 @@ class StudentPass:
                 h = ops.inject_renorm(h, icv[0, i], alpha=al)
             st["layers"].append(rec)
         st["h_final"] = h
-        xf = ops.rmsnorm(h, w.final_ln, a.rms_eps)
-        logits = ops.linear(xf.index_select(0, logits_rows), w.lm_head)
-        return logits, st
+        return lm_logits(ops.rmsnorm(h, w.final_ln, a.rms_eps), w.lm_head, B, S, logits_rows), st
 
     # ------------------------------------------------------------------ backward
     def backward(self, st: dict, dlogits_rows: torch.Tensor) -> torch.Tensor:
         """dlogits_rows: (R, V) bf16 grad wrt the logits returned by forward.  Returns d loss / d v_l for every hooked
         layer as (1, n_hooked, H) fp32, where v_l = alpha_l * icv_l is what the hook added."""
-        e, a, w, tw = self.e, self.e.arch, self.e.w, self.tw
+        a, w, tw = self.e.arch, self.e.w, self.tw
         B, S, Nk = st["B"], st["S"], st["Nk"]
-        M, H, nh, hd, I = B * S, a.hidden_size, a.num_heads, a.head_dim, a.intermediate_size
+        M, H, nh, hd = B * S, a.hidden_size, a.num_heads, a.head_dim
         dev = w.device
-        V = w.lm_head.shape[0]
-        n_hooked = len(st["idx_of"])
-        grad_v = torch.zeros((1, n_hooked, H), dtype=torch.float32, device=dev)
-        # head + final norm
-        assert dlogits_rows.shape[1] == tw.head_T.shape[1] and dlogits_rows.is_contiguous(), "pass the padded grad from ops.kl_rows_bwd"
-        d_xf_rows = ops.linear(dlogits_rows, tw.head_T)                                              # (R, H) bf16
-        d_xf = torch.zeros((M, H), dtype=torch.bfloat16, device=dev)
-        d_xf.index_copy_(0, st["logits_rows"], d_xf_rows)
-        dh = torch.empty((M, H), dtype=torch.float32, device=dev)
-        ops.rmsnorm_bwd(st["h_final"], w.final_ln, d_xf, dh, a.rms_eps, accumulate=False)
+        grad_v = torch.zeros((1, len(st["idx_of"]), H), dtype=torch.float32, device=dev)
+        dh = _head_backward(st, dlogits_rows, w, tw, M, H, a.rms_eps, 0)
         for l in reversed(range(a.num_layers)):
             rec = st["layers"][l]
             D, T = w.dec[l], tw.dec[l]
@@ -163,11 +173,7 @@ class StudentPass:
                 al = st["alpha"][0, i:i + 1] if st["alpha"] is not None else None
                 dh, gv = ops.inject_renorm_bwd(rec["h_pre_hook"], st["icv"][0, i], al, dh)
                 grad_v[0, i] = gv
-            # MLP branch
-            d_out = ops.branch_grad(dh)
-            d_act = ops.linear(d_out, T["down_T"])
-            d_gu = ops.swiglu_bwd(rec["gu"], d_act)
-            ops.rmsnorm_bwd_from(rec["h_mid"], D.post_ln, d_gu, T["gu_T"], dh, a.rms_eps, accumulate=True)
+            _mlp_backward(dh, rec["gu"], rec["h_mid"], D.post_ln, T, dh, a.rms_eps, 0)
             # attention branch
             d_o = ops.branch_grad(dh)
             d_attn = ops.linear(d_o, T["o_T"])
@@ -182,10 +188,7 @@ class StudentPass:
                 x = rec["x"]
                 j = l // a.cross_layer_interval
                 X, TX = w.xat[j], tw.xat[j]
-                d_out = ops.branch_grad(dh, scale=X.gate_dense)
-                d_act = ops.linear(d_out, TX["down_T"])
-                d_gu = ops.swiglu_bwd(x["gu"], d_act)
-                ops.rmsnorm_bwd_from(x["h_mid"], X.post_ln, d_gu, TX["gu_T"], dh, a.rms_eps, accumulate=True)
+                _mlp_backward(dh, x["gu"], x["h_mid"], X.post_ln, TX, dh, a.rms_eps, 0, scale=X.gate_dense)
                 d_o = ops.branch_grad(dh, scale=X.gate_attn, row_gate=st["gate"])
                 d_attn = ops.linear(d_o, TX["o_T"])
                 dq = torch.empty((M, H), dtype=torch.bfloat16, device=dev)
@@ -205,17 +208,9 @@ class StudentPass:
 class TrainWeights2:
     """Transposed / unfused copies of the Mistral stack's weights for the backward (Idefics2)."""
 
-    def __init__(self, w, sd: Optional[Dict[str, torch.Tensor]] = None):
-        dev = w.device
-        self.text = []
-        for i, L in enumerate(w.text):
-            gu = _unpack_gate_up(L.gu_w)                                                                 # (2I, H) gate | up
-            self.text.append(dict(gu=gu, gu_T=_t(gu), down_T=_t(L.down_w), o_T=_t(L.o_w), qkv_T=_t(L.qkv_w)))
-        V = w.lm_head.shape[0]
-        head_T = torch.zeros((w.lm_head.shape[1], (V + 7) // 8 * 8), dtype=torch.bfloat16, device=dev)
-        head_T[:, :V] = w.lm_head.t()
-        self.head_T = head_T
-        self.neg_sin = (-w.sin.float()).to(torch.bfloat16).contiguous()
+    def __init__(self, w):
+        self.text = [_transposed(L, ("down", "o", "qkv")) for L in w.text]
+        self.head_T, self.neg_sin = _head_T(w), _neg_sin(w)
 
 
 class StudentPass2:
@@ -232,8 +227,7 @@ class StudentPass2:
         dev = w.device
         B, S = input_ids.shape
         M, H, nh, nkv, hd = B * S, a.hidden_size, a.num_heads, a.num_kv_heads, a.head_dim
-        qd, kd = nh * hd, nkv * hd
-        ldq = qd + 2 * kd
+        qd = nh * hd
         ids = input_ids.to(dev).contiguous()
         with torch.no_grad():
             img = e.encode_images(pixel_values, pixel_attention_mask) if pixel_values is not None else None
@@ -243,19 +237,14 @@ class StudentPass2:
             frontend.merge_image_rows_(h, ids, img.reshape(-1, H).contiguous(), a.image_token_id)
         key_valid = attention_mask.to(device=dev, dtype=torch.int32).contiguous()
         pos = torch.arange(S, device=dev, dtype=torch.int64).repeat(B).contiguous()
-        idx_of = {int(l): i for i, l in enumerate(hook_layers)}
-        icv = icv.detach().to(device=dev, dtype=torch.float32).contiguous()
-        alpha = alpha.detach().to(device=dev, dtype=torch.float32).contiguous() if alpha is not None else None
+        idx_of, icv, alpha = hook_args(icv, alpha, hook_layers, dev)
         st = dict(B=B, S=S, key_valid=key_valid, pos=pos, icv=icv, alpha=alpha, idx_of=idx_of, layers=[], logits_rows=logits_rows)
         for l, L in enumerate(w.text):
             T = tw.text[l]
             rec = {"h_in": h}
             xn = ops.rmsnorm(h, L.in_ln, a.rms_eps, 1)
-            qkv = ops.linear(xn, L.qkv_w)
-            ops.rotary_(qkv, w.cos, w.sin, pos, M, nh + nkv, hd, ldq, 0, 1)       # Q heads | K heads contiguous in the fused row
-            rec["qkv"] = qkv
-            o = ops.attention(qkv, qkv.view(-1)[qd:], qkv.view(-1)[qd + kd:], B, S, S, nh, nkv, hd, S * ldq, ldq, S * ldq, ldq,
-                              hd ** -0.5, 1, key_valid=key_valid)
+            o, rec["qkv"] = causal_self_attention(lambda: ops.linear(xn, L.qkv_w), xn, L.qkv_w, w.cos, w.sin, pos, key_valid, B, S,
+                                                  nh, nkv, hd, (nh + nkv, 0, 1))    # Q heads | K heads contiguous in the fused row
             h = ops.linear(o.view(M, qd), L.o_w, residual=h)
             rec["h_mid"] = h
             xn = ops.rmsnorm(h, L.post_ln, a.rms_eps, 1)
@@ -272,37 +261,27 @@ class StudentPass2:
                 h = ops.linear(act, L.down_w, residual=h)
             st["layers"].append(rec)
         st["h_final"] = h
-        xf = ops.rmsnorm(h, w.final_ln, a.rms_eps, 1)
-        logits = ops.linear(xf.index_select(0, logits_rows), w.lm_head)
-        return logits, st
+        return lm_logits(ops.rmsnorm(h, w.final_ln, a.rms_eps, 1), w.lm_head, B, S, logits_rows), st
 
     def backward(self, st: dict, dlogits_rows: torch.Tensor) -> torch.Tensor:
-        e, a, w, tw = self.e, self.e.arch, self.e.w, self.tw
+        a, w, tw = self.e.arch, self.e.w, self.tw
         B, S = st["B"], st["S"]
         M, H, nh, nkv, hd = B * S, a.hidden_size, a.num_heads, a.num_kv_heads, a.head_dim
         qd, kd, rep = nh * hd, nkv * hd, nh // nkv
         ldq = qd + 2 * kd
         dev = w.device
         grad_v = torch.zeros((1, len(st["idx_of"]), H), dtype=torch.float32, device=dev)
-        assert dlogits_rows.shape[1] == tw.head_T.shape[1] and dlogits_rows.is_contiguous(), "pass the padded grad from ops.kl_rows_bwd"
-        d_xf = torch.zeros((M, H), dtype=torch.bfloat16, device=dev)
-        d_xf.index_copy_(0, st["logits_rows"], ops.linear(dlogits_rows, tw.head_T))
-        dh = torch.empty((M, H), dtype=torch.float32, device=dev)
-        ops.rmsnorm_bwd(st["h_final"], w.final_ln, d_xf, dh, a.rms_eps, accumulate=False, flavour=1)
+        dh = _head_backward(st, dlogits_rows, w, tw, M, H, a.rms_eps, 1)
         for l in reversed(range(a.num_layers)):
             rec, L, T = st["layers"][l], w.text[l], tw.text[l]
             # MLP branch: hooked -> through the edit's backward, else straight
+            d_m = dh
             if l in st["idx_of"]:
                 i = st["idx_of"][l]
                 al = st["alpha"][0, i:i + 1] if st["alpha"] is not None else None
                 d_m, gv = ops.inject_renorm_bwd(rec["m"], st["icv"][0, i], al, dh)
                 grad_v[0, i] = gv
-                d_out = ops.branch_grad(d_m)
-            else:
-                d_out = ops.branch_grad(dh)
-            d_act = ops.linear(d_out, T["down_T"])
-            d_gu = ops.swiglu_bwd(rec["gu"], d_act)
-            ops.rmsnorm_bwd_from(rec["h_mid"], L.post_ln, d_gu, T["gu_T"], dh, a.rms_eps, accumulate=True, flavour=1)
+            _mlp_backward(d_m, rec["gu"], rec["h_mid"], L.post_ln, T, dh, a.rms_eps, 1)
             # attention branch (GQA): dK / dV per query head, then the group sum = backward of repeat_kv
             d_attn = ops.linear(ops.branch_grad(dh), T["o_T"])
             qkv = rec["qkv"]
