@@ -28,7 +28,8 @@ extern "C" {
  * the CLIP text tower's kernels (licv_clip_text_embed, licv_attn_varlen_causal, licv_layernorm_rows_fwd): they only ADD symbols - no
  * existing entry point changed, so a binding written against 9 keeps working (check_exports still asks for every declared symbol); and still 9 with
  * constrained decoding: licv_logits_process is a new symbol, and licv_beam_step accepts one new VALUE of an existing field
- * (logits_dtype = LICV_F32_LOGPROBS) that no earlier caller passes - no struct changed its layout. */
+ * (logits_dtype = LICV_F32_LOGPROBS) that no earlier caller passes - no struct changed its layout; and still 9 with candidate ranking:
+ * licv_append_attn is a new symbol with a struct of its own. */
 #define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
@@ -347,7 +348,7 @@ typedef struct {
     const int32_t* hook_slot;                          /* HOST array [n_layers]: row of icv for that layer's output, -1 = not hooked */
     void* const* kv_cache;                             /* HOST array [n_layers] of (B, cache_max_len, 2*hidden) bf16, or NULL */
     int64_t cache_max_len, past;
-    const int32_t* kv_rows; int64_t ld_kv_rows;        /* decode steps (S == 1): physical cache row of every history position (licv_decode_attn), or NULL */
+    const int32_t* kv_rows; int64_t ld_kv_rows;        /* physical cache row of every history position, or NULL: decode steps (S == 1, licv_decode_attn) and continuation steps (S > 1, licv_append_attn) */
     const void* const* xkv_cached;                     /* HOST array [n_x] of projected+normed cross-attention K|V (B, Nk, 2*hidden), or NULL */
     void* const* xkv_out;                              /* HOST array [n_x]: project INTO these (they become next step's xkv_cached), or NULL */
     const int64_t* logits_rows; int64_t n_rows;        /* logits only for these flat rows (n_rows = 0: all B*S rows) */
@@ -358,7 +359,10 @@ typedef struct {
 /* Options of the runner: 0 = fold the decoder layers' two residual adds into the row kernels that follow (licv_add_rmsnorm_fwd,
  * licv_inject_renorm_pre_fwd), so the o / down projections take the register-direct GEMM epilogue (default 1; bit-identical either
  * way, 0 is for A/B timing).  1 = where the o / down / QKV projections run split-K (M < 512), let the row kernel behind each of
- * them sum the slices (the *_ws entry points) instead of a finalize launch (default 1; bit-identical). */
+ * them sum the slices (the *_ws entry points) instead of a finalize launch (default 1; bit-identical).  2 = MiB of the next
+ * projection's weights a side stream reads ahead during decode steps (default 0 = off).  3 = steps with kv_rows append
+ * their K | V to the rows' own cache rows (default 1); 0 = they only read the cache (candidate scoring on a shared prompt; they run
+ * licv_append_attn also when S == 1), which may then hold fewer rows than B. */
 int licv_runner_option(int option, int value);
 int licv_idefics_text_forward(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, void* stream);
 
@@ -380,6 +384,30 @@ typedef struct {
     float scale;
 } licv_decode_attn_args;
 int licv_decode_attn(const licv_decode_attn_args* a, void* stream);
+
+/* ---- a continuation step's self-attention block: T new tokens per row THROUGH the cache-row table, in ONE launch.  It generalises
+ * licv_decode_attn (same references, same arithmetic; T = 1 with append = 1 gives its bits) and replaces, for a step of T > 1 tokens
+ * behind a row table, the only forms available before it: a chain of T licv_decode_attn launches, which fetches the history T times,
+ * or licv_rotary_kv_append + licv_attn_fwd on a physically gathered copy of the cache.  Row r*T + t of qkv_bf16 / position_ids / out is
+ * token t of row r.  Query t of row r attends to history positions j < past, read from cache row kv_rows[r][j] (NULL: cache row r),
+ * and to the new tokens u <= t of its own row at key index past + u.  key_valid (M, past + T), optional: a key with 0 is masked for
+ * every query; the output of a query whose own key is masked is unspecified but finite.  append = 1: the rotated K and the V of the T
+ * tokens are written to cache[r, past : past+T] (the cache then needs M rows) and nothing else changes; append = 0: the cache is
+ * only read, so M rows may share the rows of a smaller cache (candidate scoring on a shared prompt).  head_dim: a multiple of 8 up
+ * to 128; (past + T) * 4 bytes <= 40 KiB as for licv_decode_attn. */
+#define LICV_APPEND_MAX_T 32
+typedef struct {
+    const void* qkv_bf16; int64_t ldq;                                   /* (M*T, ldq) bf16 rows [Q | K | V] */
+    const void* cos; const void* sin; const int64_t* position_ids; int64_t n_pos;   /* (n_pos, head_dim) bf16 tables, (M*T) positions */
+    void* cache; int64_t max_len, past;                                  /* (rows, max_len, 2 * n_kv_heads * head_dim) bf16, K then V */
+    const int32_t* kv_rows; int64_t ld_kv_rows;                          /* (M, ld_kv_rows >= past) int32, or NULL */
+    const int32_t* key_valid;                                            /* (M, past + T) attention mask, or NULL */
+    int append;                                                          /* 1: write the new K | V to cache[r, past : past+T]; 0: leave the cache alone */
+    void* out;                                                           /* (M*T, n_heads * head_dim) bf16 */
+    int64_t M, T, n_heads, n_kv_heads, head_dim;
+    float scale;
+} licv_append_attn_args;
+int licv_append_attn(const licv_append_attn_args* a, void* stream);
 
 /* ---- beam search bookkeeping of hooked generate (ref:inference.py:300-321 -> transformers GenerationMixin._beam_search, 5.x form,
  * generation/utils.py:3077-3460; ref:config/inference.yaml:26-30: 3 beams, 5 new tokens, length_penalty 0) ----

@@ -111,12 +111,16 @@ int linear_to_rows(const Ctx& x, const void* A, int64_t M, const void* W, int64_
 }  // namespace
 
 static int g_fold_residual = 1;
+static int g_append_continuation = 1;
 // option 0: fold the decoder layers' residual adds into the row kernels that follow them (default 1; 0 for A/B timing)
 // option 1: at M < 512, split-K projections leave their slices for the row kernel behind them to sum (default 1; 0 for A/B timing)
 // option 2: decode steps (M <= 32): MiB of the NEXT projection's weights a side stream reads ahead into the Infinity Cache (0 = off)
+// option 3: steps behind kv_rows: 1 = their K | V are appended to the rows' own cache rows (default), 0 = the cache is only read
+//           (candidate scoring on a shared prompt: the prefill's cache stays as it was, and may hold fewer rows than B)
 extern "C" int licv_runner_option(int option, int value) {
     if (option == 0) { g_fold_residual = value; return LICV_OK; }
     if (option == 1) { g_sum_in_rows = value; return LICV_OK; }
+    if (option == 3) { g_append_continuation = value ? 1 : 0; return LICV_OK; }
     if (option == 2) { g_pf.cap_bytes = (int64_t)(value < 0 ? 0 : value) << 20; return LICV_OK; }      // MiB of each next projection's weights to prefetch; 0 = off
     return licv_set_error(LICV_E_BADARG, "runner_option: unknown option %d", option);
 }
@@ -217,14 +221,25 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
         } else if (!xn_valid) { RUN(licv_rmsnorm_fwd(x.h, x.h_dt, D.in_ln, c->x, M, H, 1, H, H, w->rms_eps, 0, stream)); xin = c->x; }
         xn_valid = false;
         Slices qs;                                         // decode steps: the QKV slices go straight into rotary + cache append
-        if (c->kv_cache && M < 512) RUN(linear_to_rows(x, xin, M, D.qkv_w, 3 * H, H, c->qkv, &qs));
+        // S new tokens per row behind the row table (or one that must not be appended): bf16 rows, one launch (csrc/append_attn.hip)
+        const bool continuation = c->kv_cache && c->kv_rows && (S > 1 || !g_append_continuation);
+        if (c->kv_cache && M < 512 && !continuation) RUN(linear_to_rows(x, xin, M, D.qkv_w, 3 * H, H, c->qkv, &qs));
         else RUN(linear(x, xin, M, D.qkv_w, 3 * H, H, c->qkv, 3 * H, LICV_BF16));
         if (!c->kv_cache) RUN(licv_rotary_fwd(c->qkv, w->cos, w->sin, c->position_ids, M, nh, hd, 3 * H, H, 2, w->rope_len, stream));
         licv_attn_args a;
         a.q = c->qkv; a.q_bs = S * 3 * H; a.q_rs = 3 * H;
         a.o = c->o; a.B = B; a.Sq = S; a.n_heads = nh; a.n_kv_heads = nh; a.head_dim = hd; a.scale = att_scale; a.mask_mode = 1;
         a.key_valid = c->key_valid; a.img_mask = nullptr; a.n_img = 0; a.img_len = 0;
-        if (c->kv_cache && S == 1) {
+        if (continuation) {
+            licv_append_attn_args d;
+            d.qkv_bf16 = c->qkv; d.ldq = 3 * H;
+            d.cos = w->cos; d.sin = w->sin; d.position_ids = c->position_ids; d.n_pos = w->rope_len;
+            d.cache = c->kv_cache[l]; d.max_len = c->cache_max_len; d.past = c->past;
+            d.kv_rows = c->kv_rows; d.ld_kv_rows = c->ld_kv_rows; d.key_valid = c->key_valid;
+            d.append = g_append_continuation;
+            d.out = c->o; d.M = B; d.T = S; d.n_heads = nh; d.n_kv_heads = nh; d.head_dim = hd; d.scale = att_scale;
+            RUN(licv_append_attn(&d, stream));
+        } else if (c->kv_cache && S == 1) {
             // a decode step (one new token per row): rotary, the append to the row's cache and the attention over its history in ONE launch
             // (csrc/decode.hip); with c->kv_rows the history is read through the beam search's row table - the cache itself never moves
             licv_decode_attn_args d;

@@ -89,3 +89,7 @@ class LearnableICVInterventionLMM(nn.Module):
 
     def generate(self, icv=None, *args, **kwargs):
         return self._run(self.lmm.generate, icv, False, args, kwargs)
+
+    def score_candidates(self, icv=None, *args, **kwargs):
+        """Closed-set scoring of candidate answers under the hooks (the LMM interface's ``score_candidates``): ``icv`` as in ``generate``."""
+        return self._run(self.lmm.score_candidates, icv, False, args, kwargs)

@@ -98,3 +98,72 @@ def icl_inference(train_ds: Sequence[dict], val_ds: Sequence[dict], ice_idx_list
             results[index] = {"prediction": generated[i], **rec}
             index += 1
     return results
+
+
+def _tokenize_candidates(processor, texts: Sequence[Sequence[str]]):
+    """texts[b][c] -> (ids (B, C, T) int64 right padded with 0, lengths (B, C)); every question must offer the same number of candidates."""
+    C = len(texts[0])
+    if C == 0 or any(len(t) != C for t in texts):
+        raise ValueError("every sample must offer the same, non-zero number of candidates")
+    toks = [[list(processor.tokenizer(text, add_special_tokens=False)["input_ids"]) for text in row] for row in texts]
+    if any(len(t) == 0 for row in toks for t in row):
+        raise ValueError("a candidate tokenised to nothing")
+    T = max(len(t) for row in toks for t in row)
+    ids = torch.zeros((len(texts), C, T), dtype=torch.long)
+    lengths = torch.zeros((len(texts), C), dtype=torch.long)
+    for b, row in enumerate(toks):
+        for c, t in enumerate(row):
+            ids[b, c, :len(t)] = torch.tensor(t, dtype=torch.long)
+            lengths[b, c] = len(t)
+    return ids, lengths
+
+
+@torch.inference_mode()
+def rank_answers(inputs, model, processor, candidates: Sequence[Sequence[str]], in_context_vector=None, alpha=None, normalize: str = "sum"):
+    """Closed-set counterpart of `generate_answers`: ranks candidates[b] (a list of strings per prompt row of `inputs`, or one list of
+    strings offered to every row) by their
+    log-likelihood under the hooked model (`model.score_candidates`), summed over the candidate's tokens (normalize="sum") or divided
+    by their number ("mean").  The text is tokenised as given, `processor.tokenizer(text, add_special_tokens=False)`: whether a
+    candidate starts with a space is the caller's choice.  The vector handed to the hooks is alpha[..., None] * in_context_vector.
+    Returns (index of the best candidate per row, scores per row as lists of floats)."""
+    if normalize not in ("sum", "mean"):
+        raise ValueError(f"normalize must be 'sum' or 'mean', not {normalize!r}")
+    icv = None
+    if in_context_vector is not None:
+        icv = alpha.unsqueeze(dim=-1) * in_context_vector
+    if len(candidates) and isinstance(candidates[0], str):               # one list for every prompt row
+        candidates = [list(candidates)] * int(inputs["input_ids"].shape[0])
+    ids, lengths = _tokenize_candidates(processor, candidates)
+    dev = inputs["input_ids"].device
+    out = model.score_candidates(**inputs, candidates=ids.to(dev), candidate_lengths=lengths.to(dev), icv=icv)
+    scores = getattr(out, normalize)
+    return scores.argmax(-1).tolist(), scores.tolist()
+
+
+@torch.inference_mode()
+def rank_inference(val_ds: Sequence[dict], icv_model, prompt_manager, processor, bs: int, candidates, instruction: str = "",
+                   in_context_vector: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
+                   normalize: str = "sum") -> Dict[int, dict]:
+    """`icv_inference` with candidate ranking in place of generation: the same zero-shot prompts in chunks of `bs`, one result record
+    per sample: {"prediction": text of the best candidate, "scores": [score of every candidate], **sample without its image}.
+    candidates: a list of strings offered to every sample, or the name of a sample field that holds that sample's list (all lists
+    equally long).  Candidates are tokenised as given (see `rank_answers`).  As in `icv_inference` a short last chunk is still `bs`
+    prompts wide (the trailing prompts are scored against the first sample's candidates and dropped) and the samples are not mutated."""
+    results: Dict[int, dict] = {}
+    index = 0
+    for batch in _chunks(val_ds, bs):
+        prompts = [[instruction] if instruction else [] for _ in range(bs)]
+        for i, sample in enumerate(batch):
+            prompts[i].extend([sample["image"], prompt_manager.gen_query_text_without_label(sample)])
+        per_sample = [list(s[candidates]) if isinstance(candidates, str) else list(candidates) for s in batch]
+        per_sample += [per_sample[0]] * (bs - len(batch))
+        query_inputs = processor.prepare_input(prompts)
+        query_inputs = {k: v.to(icv_model.lmm.device) for k, v in query_inputs.items()}
+        best, scores = rank_answers(inputs=query_inputs, model=icv_model, processor=processor, candidates=per_sample,
+                                    in_context_vector=in_context_vector, alpha=alpha, normalize=normalize)
+        for i in range(len(batch)):
+            rec = dict(batch[i])
+            rec.pop("image")
+            results[index] = {"prediction": per_sample[i][best[i]], "scores": scores[i], **rec}
+            index += 1
+    return results

@@ -90,6 +90,18 @@ class DecodeAttnArgs(C.Structure):
                 ("M", C.c_int64), ("n_heads", C.c_int64), ("n_kv_heads", C.c_int64), ("head_dim", C.c_int64), ("scale", C.c_float)]
 
 
+APPEND_MAX_T = 32        # == LICV_APPEND_MAX_T: new tokens per row of one licv_append_attn call
+
+
+class AppendAttnArgs(C.Structure):
+    _fields_ = [("qkv_bf16", C.c_void_p), ("ldq", C.c_int64),
+                ("cos", C.c_void_p), ("sin", C.c_void_p), ("position_ids", C.c_void_p), ("n_pos", C.c_int64),
+                ("cache", C.c_void_p), ("max_len", C.c_int64), ("past", C.c_int64),
+                ("kv_rows", C.c_void_p), ("ld_kv_rows", C.c_int64), ("key_valid", C.c_void_p), ("append", C.c_int), ("out", C.c_void_p),
+                ("M", C.c_int64), ("T", C.c_int64), ("n_heads", C.c_int64), ("n_kv_heads", C.c_int64), ("head_dim", C.c_int64),
+                ("scale", C.c_float)]
+
+
 def declared_symbols(header: Path = HEADER):
     """Every function name declared in include/licv_hip.h (or the given header)."""
     text = header.read_text()
@@ -162,6 +174,7 @@ def lib() -> C.CDLL:
             "licv_sample_step": [C.POINTER(SampleStepArgs), C.POINTER(SampleParams), P],
             "licv_beam_sample_step": [C.POINTER(BeamStepArgs), C.POINTER(SampleParams), P],
             "licv_decode_attn": [C.POINTER(DecodeAttnArgs), P],
+            "licv_append_attn": [C.POINTER(AppendAttnArgs), P],
             "licv_embed_gather": [P, P, P, P, I64, I64, I64, I64, P],
             "licv_im2col_patches": [P, P, I64, I64, I64, I64, I64, P],
             "licv_vit_embed_ln": [P, P, P, P, P, P, I64, I64, I64, F, P],

@@ -98,16 +98,23 @@ def encoder_layer_(x: torch.Tensor, L: EncoderLayer, eps: float, act: str, atten
 # ------------------------------------------------------------------------------------------------ text stacks
 def causal_self_attention(project, x, qkv_w: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
                           key_valid: torch.Tensor, B: int, S: int, n_heads: int, n_kv_heads: int, head_dim: int, rotary,
-                          cache: Optional[torch.Tensor] = None, kv_rows: Optional[torch.Tensor] = None, past: int = 0):
+                          cache: Optional[torch.Tensor] = None, kv_rows: Optional[torch.Tensor] = None, past: int = 0,
+                          append: bool = True):
     """Rotary + causal attention of one decoder layer on the fused projection [Q | K | V] of the normed rows x: (o, rotated qkv).
     project() -> the (B * S, (n_heads + 2 n_kv_heads) * head_dim) bf16 rows x @ qkv_w.T, by whichever GEMM the caller routes it to.
     rotary = (n_heads, tensor_stride, n_tensors) of the ops.rotary_ launch over Q and K.  cache: this layer's (rows, max_len, [K | V])
     tensor or None.  No cache: attention among the S new tokens.  Cache and S > 1 (prefill): K | V appended at `past`, attention over
     the cache.  Cache and S == 1 (a decode step): rotary + append + attention in one launch, fed by the split-K slices of the
-    projection where the plan splits it; no qkv tensor exists then (None)."""
+    projection where the plan splits it; no qkv tensor exists then (None).  Cache, a row table and S > 1 (a continuation step of S
+    tokens per row behind shared history): rotary + attention through the table in one launch (ops.append_attn); `append` says whether
+    the S tokens' K | V go into the row's own cache row - a scoring pass leaves the cache as it found it, also when S == 1 (the decode
+    launch always appends, and the rows of a scoring pass have no cache row of their own).  No rotated qkv exists (None)."""
     nh, nkv, hd = n_heads, n_kv_heads, head_dim
     qd, kd = nh * hd, nkv * hd
     ldq = qd + 2 * kd
+    if cache is not None and kv_rows is not None and (S > 1 or not append):
+        return ops.append_attn(project(), cos, sin, pos, cache, past, S, nh, nkv, hd, hd ** -0.5, key_valid=key_valid, kv_rows=kv_rows,
+                               append=append), None
     if cache is not None and S == 1:
         qs = ops.linear_produce(x, qkv_w) if not isinstance(x, tuple) else None
         return ops.decode_attn(qs if qs is not None else project(), cos, sin, pos, cache, past, nh, nkv, hd, hd ** -0.5,

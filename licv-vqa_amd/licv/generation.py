@@ -9,6 +9,7 @@ steps on (B*beams, 1) with the ICV hook firing at every step, as in the referenc
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
@@ -18,6 +19,24 @@ from .idefics_engine import IdeficsEngine, KVCache
 
 def _last_rows(B: int, S: int, dev) -> torch.Tensor:
     return torch.arange(B, device=dev) * S + (S - 1)
+
+
+class _shared_prompt:
+    """For one continuation step: the cache's row table maps row r to the prompt row r // cc, and nothing is appended.  The cache (rows,
+    len, cross-attention K|V) is as before afterwards."""
+
+    def __init__(self, cache: KVCache, cc: int):
+        self.cache, self.cc = cache, cc
+
+    def __enter__(self):
+        c = self.cache
+        self.saved = (c.rows, c.append, c.xkv)
+        own = torch.arange(c.batch * self.cc, device=c._all.device, dtype=torch.int32) // self.cc
+        c.rows, c.append = own.unsqueeze(1).repeat(1, c.max_len).contiguous(), False
+
+    def __exit__(self, *exc):
+        self.cache.rows, self.cache.append, self.cache.xkv = self.saved
+        return False
 
 
 class _IdeficsDecoder:
@@ -41,6 +60,17 @@ class _IdeficsDecoder:
 
     def step(self, new_ids, am):
         return self._fwd(new_ids, am, self.iam)
+
+    def continuation(self, ids, am, cc, rows):
+        """Logits rows `rows` of a continuation step on `cc` candidates per question: (B*cc, Tc) tokens behind the shared prompt.  Every
+        token takes the image-mask row of the prompt's last token; a question's image states and cross-attention K|V are repeated."""
+        Tc = ids.shape[1]
+        rep = lambda t: t.repeat_interleave(cc, 0)
+        with _shared_prompt(self.cache, cc):
+            if self.cache.xkv is not None:
+                self.cache.xkv = [rep(t) for t in self.cache.xkv]
+            return self.e.forward(input_ids=ids, attention_mask=am, image_states=rep(self.image_states),
+                                  image_attention_mask=rep(self.iam.expand(-1, Tc, -1)), kv_cache=self.cache, logits_rows=rows, **self.hooks)
 
     def replicate(self, nb):                       # HF prefills B*nb identical rows; replicate the prompt state instead
         self.cache.replicate(nb)
@@ -86,6 +116,14 @@ class _Idefics2Decoder:
         self.pos = self.pos + 1
         return self._fwd(new_ids, am, None)
 
+    def continuation(self, ids, am, cc, rows):
+        """As _IdeficsDecoder.continuation; the positions go on from the prompt's last one, as in a chain of decode steps."""
+        Tc = ids.shape[1]
+        pos = (self.pos + 1 + torch.arange(Tc, device=self.pos.device)).repeat_interleave(cc, 0)
+        with _shared_prompt(self.cache, cc):
+            return self.e.forward(input_ids=ids, attention_mask=am, image_hidden_states=None, position_ids=pos, kv_cache=self.cache,
+                                  logits_rows=rows, **self.hooks)
+
     def replicate(self, nb):
         self.cache.replicate(nb)
         self.pos = self.pos.repeat_interleave(nb, 0)
@@ -120,6 +158,99 @@ def generate_idefics2(engine, input_ids: torch.Tensor, attention_mask: torch.Ten
     hooks = dict(icv=icv, hook_layers=hook_layers) if icv is not None else {}
     model = _Idefics2Decoder(engine, pixel_values, pixel_attention_mask, input_ids.shape[0], input_ids.shape[1] + max_new_tokens, hooks, beams=num_beams)
     return _decode(model, engine.arch, input_ids, attention_mask, max_new_tokens=max_new_tokens, num_beams=num_beams, **kw)
+
+
+@dataclass
+class ContinuationScores:
+    """token_logprobs (B, C, T) fp32: log p(candidate token | prompt, earlier candidate tokens), zero at padding; sum (B, C); mean (B, C):
+    the sum divided by the candidate's length."""
+    token_logprobs: torch.Tensor
+    sum: torch.Tensor
+    mean: torch.Tensor
+
+
+# Rows (questions x candidates of a chunk) of one continuation pass.  Every pass streams all weights once whatever its row count, so
+# a chunk should be large; 512 rows of a few tokens each are a few thousand GEMM rows, enough to amortise that stream, and bound the
+# pass's scratch (rows x tokens x the hidden / MLP widths, and its logits rows x vocabulary) to that of a prefill of that many tokens.
+DEFAULT_MAX_ROWS = 512
+
+
+def _score(model, input_ids, attention_mask, candidates, candidate_lengths, max_rows) -> ContinuationScores:
+    from . import ops
+    from ._lib import APPEND_MAX_T
+    dev = input_ids.device
+    B, P = input_ids.shape
+    if candidates.dim() != 3 or candidates.shape[0] != B or tuple(candidate_lengths.shape) != tuple(candidates.shape[:2]):
+        raise ValueError(f"candidates must be (B, C, T) and candidate_lengths (B, C); got {tuple(candidates.shape)} and {tuple(candidate_lengths.shape)}")
+    lens = candidate_lengths.to(device=dev, dtype=torch.long)
+    C, T_in = candidates.shape[1:]
+    lo, hi = int(lens.min()), int(lens.max())
+    if lo < 1 or hi > T_in:
+        raise ValueError(f"every candidate length must lie in [1, {T_in}]; got {lo} .. {hi}")
+    if bool((attention_mask[:, -1] == 0).any()):
+        raise ValueError("prompts must be left padded: the last column of attention_mask is masked for some row")
+    T = hi                                                                 # columns that are padding for every candidate are dropped
+    Tc = T - 1
+    if Tc > APPEND_MAX_T:
+        raise ValueError(f"candidates of {T} tokens need a continuation step of {Tc} tokens; the limit is LICV_APPEND_MAX_T = {APPEND_MAX_T}")
+    if max_rows < B:
+        raise ValueError(f"max_rows = {max_rows} is smaller than the batch of {B} prompts")
+    tok_valid = torch.arange(T, device=dev)[None, None, :] < lens[:, :, None]                  # (B, C, T)
+    cand = torch.where(tok_valid, candidates[:, :, :T].to(device=dev, dtype=torch.long), torch.zeros((), dtype=torch.long, device=dev))
+    logits0 = model.prefill(input_ids, attention_mask)                    # (B, V): the prompt's last row, shared by a question's candidates
+    V = logits0.shape[1]
+    lp = torch.zeros((B, C, T), dtype=torch.float32, device=dev)
+    first = ops.ce_rows(logits0, torch.arange(B, device=dev).repeat_interleave(C), cand[:, :, 0].reshape(-1), V)
+    lp[:, :, 0] = -first.view(B, C)
+    if Tc > 0:
+        chunk = max(1, min(C, max_rows // B))
+        for c0 in range(0, C, chunk):
+            c1 = min(C, c0 + chunk)
+            cc = c1 - c0
+            ids = cand[:, c0:c1, :Tc].reshape(B * cc, Tc).contiguous()
+            am = torch.cat([attention_mask.repeat_interleave(cc, 0), tok_valid[:, c0:c1, :Tc].reshape(B * cc, Tc).to(attention_mask.dtype)], 1)
+            # flat row r * Tc + t predicts candidate token t + 1: the LM head runs on the rows whose target is a real token only
+            sel = tok_valid[:, c0:c1, 1:].reshape(-1).nonzero().squeeze(1)
+            if sel.numel() == 0:
+                continue
+            logits = model.continuation(ids, am, cc, sel)
+            ce = ops.ce_rows(logits, torch.arange(sel.numel(), device=dev), cand[:, c0:c1, 1:].reshape(-1)[sel], V)
+            flat = torch.zeros((B * cc * Tc,), dtype=torch.float32, device=dev)
+            flat[sel] = -ce
+            lp[:, c0:c1, 1:] = flat.view(B, cc, Tc)
+    total = lp.sum(-1)
+    return ContinuationScores(lp, total, total / lens.to(torch.float32))
+
+
+@torch.no_grad()
+def score_continuations(engine: IdeficsEngine, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: torch.Tensor,
+                        image_attention_mask: torch.Tensor, candidates: torch.Tensor, candidate_lengths: torch.Tensor,
+                        icv: Optional[torch.Tensor] = None, hook_layers: Optional[Sequence[int]] = None,
+                        max_rows: int = DEFAULT_MAX_ROWS) -> ContinuationScores:
+    """Closed-set scoring under the hooked model: the log-likelihood of every candidate answer given its question's prompt.
+    Model inputs as `generate` (prompts left padded); candidates (B, C, T) int64 right padded, candidate_lengths (B, C) >= 1.  One
+    prefill on the B prompts; token 0 of every candidate is scored from the prompt's last row; tokens 1 .. T-1 from ONE continuation
+    pass per chunk of candidates on tokens 0 .. T-2, which reads the prompt's KV cache through a row table (licv_append_attn) and
+    appends nothing - no pass at all when every candidate is one token long.  The hook fires on every token.  max_rows bounds
+    B * (candidates per chunk); see DEFAULT_MAX_ROWS."""
+    hooks = dict(icv=icv, hook_layers=hook_layers) if icv is not None else {}
+    T = candidates.shape[-1] if candidates.dim() == 3 else 1
+    model = _IdeficsDecoder(engine, pixel_values, image_attention_mask, input_ids.shape[0], input_ids.shape[1] + max(T - 1, 1), hooks)
+    return _score(model, input_ids, attention_mask, candidates, candidate_lengths, max_rows)
+
+
+@torch.no_grad()
+def score_continuations_idefics2(engine, input_ids: torch.Tensor, attention_mask: torch.Tensor, pixel_values: Optional[torch.Tensor] = None,
+                                 pixel_attention_mask: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
+                                 candidate_lengths: Optional[torch.Tensor] = None, icv: Optional[torch.Tensor] = None,
+                                 hook_layers: Optional[Sequence[int]] = None, max_rows: int = DEFAULT_MAX_ROWS) -> ContinuationScores:
+    """score_continuations for Idefics2 (model inputs as `generate_idefics2`)."""
+    if candidates is None or candidate_lengths is None:
+        raise ValueError("candidates and candidate_lengths are required")
+    hooks = dict(icv=icv, hook_layers=hook_layers) if icv is not None else {}
+    T = candidates.shape[-1] if candidates.dim() == 3 else 1
+    model = _Idefics2Decoder(engine, pixel_values, pixel_attention_mask, input_ids.shape[0], input_ids.shape[1] + max(T - 1, 1), hooks)
+    return _score(model, input_ids, attention_mask, candidates, candidate_lengths, max_rows)
 
 
 def sample_params(temperature=None, top_k=None, top_p=None, min_p=None, seed=None):

@@ -329,7 +329,7 @@ class Idefics2Engine:
             assert pos.numel() == M
         idx_of, icv, alpha = hook_args(icv, alpha, hook_layers, dev)
         qd = nh * hd
-        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past)
+        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past, append=kv_cache.appending)
         xn = None
         for l, L in enumerate(w.text):
             if xn is not None:
@@ -374,7 +374,7 @@ class Idefics2Engine:
             del act
             if capture is not None:
                 capture.setdefault("layer_out", []).append(h.view(B, S, H).clone())
-        if kv_cache is not None:
+        if kv_cache is not None and kv_cache.appending:
             kv_cache.len = Sk
         x = xn if xn is not None else ops.rmsnorm(h, w.final_ln, a.rms_eps, 1)
         if capture is not None:

@@ -125,7 +125,13 @@ class KVCache:
         self._all = torch.empty((arch.num_layers, batch * beams, max_len, width), dtype=torch.bfloat16, device=device)
         self.kv = [t[:batch] for t in self._all.unbind(0)]          # the prefill's view: the first `batch` rows of every layer
         self.rows = None       # (batch * beams, max_len) int32 after replicate(); None: every row reads its own cache row
+        self.append = True     # False: a step behind `rows` reads the cache and leaves it, and `len`, alone (candidate scoring)
         self.xkv = None        # cross-attention K|V per gated layer, projected once at the prefill by the native runner (step-invariant)
+
+    @property
+    def appending(self) -> bool:
+        """Whether a forward on this cache appends its tokens (always, except behind a row table with `append` off)."""
+        return self.append or self.rows is None
 
     def replicate(self, nb: int):
         """The prompt state of every question is shared by its `nb` beams: no copy, only the row table."""
@@ -303,7 +309,7 @@ class IdeficsEngine:
                 return w.xat[(l + 1) // a.cross_layer_interval].in_ln
             return w.dec[l + 1].in_ln
 
-        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past)
+        cached = lambda l: {} if kv_cache is None else dict(cache=kv_cache.kv[l], kv_rows=kv_cache.rows, past=past, append=kv_cache.appending)
         foldable = M >= FOLD_MIN_ROWS and capture is None and save_hook_inputs is None and self.fuse_hook_norm
         pending = None                               # a cross layer's MLP branch (and its gate scale) waiting for the next norm to add it
         for l in range(a.num_layers):
@@ -373,7 +379,7 @@ class IdeficsEngine:
                     h = ops.inject_renorm(h, icv[0, i], alpha=al, out=h if in_place else None)
             if capture is not None:
                 capture.setdefault("edited", []).append(h.view(B, S, H).clone())
-        if kv_cache is not None:
+        if kv_cache is not None and kv_cache.appending:
             kv_cache.len = past + S
         x = xn if xn is not None else ops.rmsnorm(h, w.final_ln, a.rms_eps)
         if capture is not None:

@@ -359,6 +359,37 @@ def decode_attn(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.T
     return out
 
 
+def append_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, cache: torch.Tensor, past: int, T: int,
+                n_heads: int, n_kv_heads: int, head_dim: int, scale: float, key_valid: Optional[torch.Tensor] = None,
+                kv_rows: Optional[torch.Tensor] = None, append: bool = True) -> torch.Tensor:
+    """A continuation step's attention block in one launch (licv_append_attn): qkv = the (M*T, [Q | K | V]) bf16 rows of the fused
+    projection, row r*T + t = token t of row r; rotary, attention of token t over the history positions < past (read through kv_rows when
+    given) and the new tokens <= t of its own row.  append: K | V of the T tokens are written to cache[r, past : past+T] (the cache needs
+    M rows); otherwise the cache is only read and M rows may share a smaller cache through kv_rows.  Returns O (M*T, n_heads * head_dim)."""
+    from ._lib import AppendAttnArgs
+    kd = n_kv_heads * head_dim
+    assert cache.dtype == torch.bfloat16 and cache.is_contiguous() and cache.shape[2] == 2 * kd
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 2 and qkv.stride(1) == 1 and T >= 1 and qkv.shape[0] % T == 0
+    M = qkv.shape[0] // T
+    assert position_ids.numel() == M * T and position_ids.dtype == torch.int64 and position_ids.is_contiguous()
+    assert (cache.shape[0] >= M) if (append or kv_rows is None) else True, "appending (or reading without a row table) needs a cache row per row"
+    a = AppendAttnArgs()
+    a.qkv_bf16, a.ldq = qkv.data_ptr(), qkv.stride(0)
+    out = torch.empty((M * T, n_heads * head_dim), dtype=torch.bfloat16, device=cache.device)
+    a.cos, a.sin, a.position_ids, a.n_pos = cos.data_ptr(), sin.data_ptr(), position_ids.data_ptr(), cos.shape[0]
+    a.cache, a.max_len, a.past = cache.data_ptr(), cache.shape[1], int(past)
+    if kv_rows is not None:
+        assert kv_rows.dtype == torch.int32 and kv_rows.is_contiguous() and kv_rows.shape[0] >= M
+        a.kv_rows, a.ld_kv_rows = kv_rows.data_ptr(), kv_rows.shape[1]
+    if key_valid is not None:
+        assert key_valid.dtype == torch.int32 and key_valid.is_contiguous() and key_valid.shape == (M, past + T)
+        a.key_valid = key_valid.data_ptr()
+    a.append = 1 if append else 0
+    a.out, a.M, a.T, a.n_heads, a.n_kv_heads, a.head_dim, a.scale = out.data_ptr(), M, int(T), n_heads, n_kv_heads, head_dim, float(scale)
+    check(_lib.lib().licv_append_attn(C.byref(a), _stream(cache)))
+    return out
+
+
 def quantize_fp8(x: torch.Tensor):
     """Per-row dynamic quantisation to OCP e4m3: returns (q uint8 (rows, K), scale fp32 (rows,))."""
     assert x.dim() == 2 and x.stride(1) == 1

@@ -116,8 +116,9 @@ class TextRunner:
         if kv_cache is not None:
             kv_arr = (P * a.num_layers)(*[t.data_ptr() for t in kv_cache.kv])
             c.kv_cache, c.cache_max_len, c.past = kv_arr, kv_cache.max_len, kv_cache.len
-            if S == 1 and getattr(kv_cache, "rows", None) is not None:   # decode step of a beam search: history read through the row table
+            if getattr(kv_cache, "rows", None) is not None:              # a step behind the row table: history read through it
                 c.kv_rows, c.ld_kv_rows = kv_cache.rows.data_ptr(), kv_cache.rows.shape[1]
+                check(_lib.lib().licv_runner_option(3, 1 if kv_cache.append else 0))     # whether this step's tokens join the cache
             if getattr(kv_cache, "xkv", None) is not None:               # cross-attention K|V projected at the prefill
                 xc_arr = (P * n_x)(*[t.data_ptr() for t in kv_cache.xkv])
                 c.xkv_cached = xc_arr
@@ -137,7 +138,7 @@ class TextRunner:
         logits = torch.empty((rows, ldc), **bf)
         c.logits, c.ld_logits = logits.data_ptr(), ldc
         check(self._fn(C.byref(self._W), C.byref(c), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        if kv_cache is not None:
+        if kv_cache is not None and kv_cache.appending:
             kv_cache.len += S
         out = logits if ldc == V else logits[:, :V]
         return out if logits_rows is not None else logits_view(out, B, S)

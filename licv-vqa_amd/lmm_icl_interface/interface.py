@@ -228,6 +228,18 @@ class IdeficsInterface(LMMInterface):
                                pad_token_id=pad_token_id if pad_token_id is not None else getattr(self.tokenizer, "pad_token_id", None),
                                **sampling, **self._hooks())
 
+    @torch.no_grad()
+    def score_candidates(self, input_ids=None, attention_mask=None, pixel_values=None, image_attention_mask=None, candidates=None,
+                         candidate_lengths=None, max_rows=None, **_):
+        """Closed-set scoring (licv.generation.score_continuations): log-likelihood of every candidate answer under the (hooked) model.
+        Model inputs as `generate` (left-padded prompts); candidates (B, C, T) int64 right padded, candidate_lengths (B, C).  Returns
+        a licv.generation.ContinuationScores (token_logprobs, sum, mean).  Installed hooks apply to every token, as in `generate`."""
+        from licv.generation import DEFAULT_MAX_ROWS, score_continuations
+        dev = self._device
+        return score_continuations(self.engine, input_ids.to(dev), attention_mask.to(dev), pixel_values.to(dev),
+                                   self._image_mask(input_ids, pixel_values, image_attention_mask), candidates.to(dev),
+                                   candidate_lengths.to(dev), max_rows=DEFAULT_MAX_ROWS if max_rows is None else max_rows, **self._hooks())
+
 
 # transformers' sampling warpers the native path does not build (hf:generation/utils.py _get_logits_processor): with do_sample they
 # raise instead of being dropped
@@ -312,3 +324,15 @@ class Idefics2Interface(IdeficsInterface):
                                  eos_token_id=eos_token_id if eos_token_id is not None else getattr(self.tokenizer, "eos_token_id", None),
                                  pad_token_id=pad_token_id if pad_token_id is not None else getattr(self.tokenizer, "pad_token_id", None),
                                  **sampling, **self._hooks())
+
+    @torch.no_grad()
+    def score_candidates(self, input_ids=None, attention_mask=None, pixel_values=None, pixel_attention_mask=None, candidates=None,
+                         candidate_lengths=None, max_rows=None, **_):
+        """IdeficsInterface.score_candidates for Idefics2 (licv.generation.score_continuations_idefics2)."""
+        from licv.generation import DEFAULT_MAX_ROWS, score_continuations_idefics2
+        dev = self._device
+        return score_continuations_idefics2(self.engine, input_ids.to(dev), attention_mask.to(dev),
+                                            pixel_values.to(dev) if pixel_values is not None else None,
+                                            pixel_attention_mask.to(dev) if pixel_attention_mask is not None else None,
+                                            candidates=candidates.to(dev), candidate_lengths=candidate_lengths.to(dev),
+                                            max_rows=DEFAULT_MAX_ROWS if max_rows is None else max_rows, **self._hooks())
