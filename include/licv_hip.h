@@ -29,7 +29,8 @@ extern "C" {
  * existing entry point changed, so a binding written against 9 keeps working (check_exports still asks for every declared symbol); and still 9 with
  * constrained decoding: licv_logits_process is a new symbol, and licv_beam_step accepts one new VALUE of an existing field
  * (logits_dtype = LICV_F32_LOGPROBS) that no earlier caller passes - no struct changed its layout; and still 9 with candidate ranking:
- * licv_append_attn is a new symbol with a struct of its own. */
+ * licv_append_attn is a new symbol with a struct of its own; and still 9 with decode steps over long histories:
+ * licv_decode_attn_split_plan and licv_decode_attn_split are new symbols that take licv_decode_attn_args as it is. */
 #define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
@@ -371,7 +372,9 @@ int licv_idefics_text_forward(const licv_idefics_text_weights* w, const licv_ide
  * (bf16, or the fp32 split-K slices of licv_gemm_bf16_splitk_produce) -> rotary on Q / K -> K | V appended to cache[r, past] -> attention
  * of the new query over positions 0..past -> out (M, n_heads * head_dim) bf16.  cache: (rows, max_len, 2 * n_kv_heads * head_dim) bf16,
  * K then V.  kv_rows (M, ld_kv_rows) int32, optional: the physical cache row holding position p of row r's history (beam search keeps
- * the cache in place and reorders this table, see licv_beam_step); NULL = every row reads its own cache row. */
+ * the cache in place and reorders this table, see licv_beam_step); NULL = every row reads its own cache row.  The kernel keeps a
+ * row's whole table in LDS: (past + 1) * 4 bytes <= 40 KiB, i.e. at most 10 240 keys, and LICV_E_BADARG beyond; a longer history goes
+ * through licv_decode_attn_split below, which has no such limit. */
 typedef struct {
     const float* qkv_ws; int splits; int64_t slice_elems, row_stride;   /* split-K slices of the QKV projection, or NULL */
     const void* qkv_bf16; int64_t ldq;                                   /* (M, ldq) bf16 rows [Q | K | V] when qkv_ws == NULL */
@@ -385,6 +388,24 @@ typedef struct {
 } licv_decode_attn_args;
 int licv_decode_attn(const licv_decode_attn_args* a, void* stream);
 
+/* ---- the same decode step over a history of ANY length, as two launches: the key range of every (row, kv head) is cut into n_splits
+ * runs of whole 64-key sweeps; every split leaves an un-normalised partial per query head (running max, running sum, head_dim fp32
+ * output columns) in `workspace`, and a second launch merges them in split order (Mx = max m_s; out = bf16(sum w_s o_s / sum w_s l_s),
+ * w_s = exp2(m_s - Mx), 0 where the sum is not positive).  No workgroup waits for another and there are no atomics: the result is a
+ * function of the arguments alone.  Same struct, same references and per-key arithmetic, same checks as licv_decode_attn except the
+ * history limit; n_splits = 1 gives licv_decode_attn's bits, and every n_splits gives its cache.  A sweep's row-table entries and
+ * key_valid flags are read when the sweep is requested, masked keys fetch no K / V, and only the split that holds position `past`
+ * appends the new token's K | V.
+ * licv_decode_attn_split_plan: the number of splits the library would choose for M rows over Sk = past + 1 keys (into *n_splits, may be
+ * NULL) and the workspace bytes for it, M * n_heads * n_splits * (head_dim + 2) * 4; a pure function of its arguments (0 and 0 splits
+ * for a non-positive argument).
+ * licv_decode_attn_split: n_splits <= 0 takes the plan's choice; a value above the number of 64-key sweeps is clamped to it, one above
+ * LICV_DECODE_MAX_SPLITS is LICV_E_BADARG.  workspace: 16-byte aligned, at least M * n_heads * n_splits * (head_dim + 2) * 4 bytes
+ * with n_splits after clamping; its content before the call does not matter and is unspecified after it. */
+#define LICV_DECODE_MAX_SPLITS 32
+int64_t licv_decode_attn_split_plan(int64_t M, int64_t n_heads, int64_t n_kv_heads, int64_t head_dim, int64_t Sk, int* n_splits);
+int licv_decode_attn_split(const licv_decode_attn_args* a, int n_splits, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- a continuation step's self-attention block: T new tokens per row THROUGH the cache-row table, in ONE launch.  It generalises
  * licv_decode_attn (same references, same arithmetic; T = 1 with append = 1 gives its bits) and replaces, for a step of T > 1 tokens
  * behind a row table, the only forms available before it: a chain of T licv_decode_attn launches, which fetches the history T times,
@@ -394,7 +415,8 @@ int licv_decode_attn(const licv_decode_attn_args* a, void* stream);
  * every query; the output of a query whose own key is masked is unspecified but finite.  append = 1: the rotated K and the V of the T
  * tokens are written to cache[r, past : past+T] (the cache then needs M rows) and nothing else changes; append = 0: the cache is
  * only read, so M rows may share the rows of a smaller cache (candidate scoring on a shared prompt).  head_dim: a multiple of 8 up
- * to 128; (past + T) * 4 bytes <= 40 KiB as for licv_decode_attn. */
+ * to 128; (past + T) * 4 bytes <= 40 KiB as for licv_decode_attn.  That limit stays: there is no split form of this entry, so candidate
+ * scoring on a prompt of more than 10 240 keys is not served (licv_decode_attn_split covers decode steps, T = 1 with append, only). */
 #define LICV_APPEND_MAX_T 32
 typedef struct {
     const void* qkv_bf16; int64_t ldq;                                   /* (M*T, ldq) bf16 rows [Q | K | V] */

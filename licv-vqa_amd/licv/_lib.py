@@ -90,6 +90,7 @@ class DecodeAttnArgs(C.Structure):
                 ("M", C.c_int64), ("n_heads", C.c_int64), ("n_kv_heads", C.c_int64), ("head_dim", C.c_int64), ("scale", C.c_float)]
 
 
+DECODE_MAX_SPLITS = 32   # == LICV_DECODE_MAX_SPLITS: splits of a (row, kv head)'s key range in licv_decode_attn_split
 APPEND_MAX_T = 32        # == LICV_APPEND_MAX_T: new tokens per row of one licv_append_attn call
 
 
@@ -127,6 +128,8 @@ def lib() -> C.CDLL:
         _lib.licv_beam_step_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
         _lib.licv_beam_sample_scratch_bytes.restype = C.c_int64
         _lib.licv_beam_sample_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
+        _lib.licv_decode_attn_split_plan.restype = C.c_int64
+        _lib.licv_decode_attn_split_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int)]
         P, I64, F, I = C.c_void_p, C.c_int64, C.c_float, C.c_int
         sig = {
             "licv_inject_renorm_fwd": [P, I, P, P, P, I64, I64, P, P, F, P],
@@ -174,6 +177,7 @@ def lib() -> C.CDLL:
             "licv_sample_step": [C.POINTER(SampleStepArgs), C.POINTER(SampleParams), P],
             "licv_beam_sample_step": [C.POINTER(BeamStepArgs), C.POINTER(SampleParams), P],
             "licv_decode_attn": [C.POINTER(DecodeAttnArgs), P],
+            "licv_decode_attn_split": [C.POINTER(DecodeAttnArgs), I, P, I64, P],
             "licv_append_attn": [C.POINTER(AppendAttnArgs), P],
             "licv_embed_gather": [P, P, P, P, I64, I64, I64, I64, P],
             "licv_im2col_patches": [P, P, I64, I64, I64, I64, I64, P],

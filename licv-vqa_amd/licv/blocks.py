@@ -117,6 +117,10 @@ def causal_self_attention(project, x, qkv_w: torch.Tensor, cos: torch.Tensor, si
                                append=append), None
     if cache is not None and S == 1:
         qs = ops.linear_produce(x, qkv_w) if not isinstance(x, tuple) else None
+        min_keys, n_splits = ops.decode_split_settings()
+        if past + 1 >= min_keys:                          # a long history (by default: one decode_attn refuses): split keys + merge
+            return ops.decode_attn_split(qs if qs is not None else project(), cos, sin, pos, cache, past, nh, nkv, hd, hd ** -0.5,
+                                         key_valid=key_valid, kv_rows=kv_rows, n_splits=n_splits), None
         return ops.decode_attn(qs if qs is not None else project(), cos, sin, pos, cache, past, nh, nkv, hd, hd ** -0.5,
                                key_valid=key_valid, kv_rows=kv_rows), None
     qkv = project()

@@ -326,12 +326,8 @@ def rotary_kv_append(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: to
     return qkv
 
 
-def decode_attn(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, cache: torch.Tensor, past: int, n_heads: int,
-                n_kv_heads: int, head_dim: int, scale: float, key_valid: Optional[torch.Tensor] = None,
-                kv_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """One decode step's attention block in one launch (licv_decode_attn): qkv = the (M, [Q | K | V]) bf16 rows of the fused projection or
-    its split-K Slices; rotary, K | V appended to cache[r, past], attention over positions 0..past (read through kv_rows when given).
-    cache: (rows >= M, max_len, 2 * n_kv_heads * head_dim) bf16.  Returns O (M, n_heads * head_dim) bf16."""
+def _decode_attn_args(qkv, cos, sin, position_ids, cache, past, n_heads, n_kv_heads, head_dim, scale, key_valid, kv_rows):
+    """(licv_decode_attn_args, out, M) of a decode step, for licv_decode_attn and licv_decode_attn_split alike."""
     from ._lib import DecodeAttnArgs
     kd = n_kv_heads * head_dim
     assert cache.dtype == torch.bfloat16 and cache.is_contiguous() and cache.shape[2] == 2 * kd
@@ -355,7 +351,79 @@ def decode_attn(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.T
         assert key_valid.dtype == torch.int32 and key_valid.is_contiguous() and key_valid.shape == (M, past + 1)
         a.key_valid = key_valid.data_ptr()
     a.out, a.M, a.n_heads, a.n_kv_heads, a.head_dim, a.scale = out.data_ptr(), M, n_heads, n_kv_heads, head_dim, float(scale)
+    return a, out, M
+
+
+def decode_attn(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, cache: torch.Tensor, past: int, n_heads: int,
+                n_kv_heads: int, head_dim: int, scale: float, key_valid: Optional[torch.Tensor] = None,
+                kv_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One decode step's attention block in one launch (licv_decode_attn): qkv = the (M, [Q | K | V]) bf16 rows of the fused projection or
+    its split-K Slices; rotary, K | V appended to cache[r, past], attention over positions 0..past (read through kv_rows when given).
+    cache: (rows >= M, max_len, 2 * n_kv_heads * head_dim) bf16.  Returns O (M, n_heads * head_dim) bf16."""
+    a, out, M = _decode_attn_args(qkv, cos, sin, position_ids, cache, past, n_heads, n_kv_heads, head_dim, scale, key_valid, kv_rows)
     check(_lib.lib().licv_decode_attn(C.byref(a), _stream(cache)))
+    return out
+
+
+DECODE_SPLIT_MIN_KEYS = 10241     # the first history length licv_decode_attn refuses (its row table must fit 40 KiB of LDS)
+
+
+class _DecodeSplit:
+    """Process-wide routing of decode steps (blocks.causal_self_attention): a step over past + 1 >= min_keys keys takes
+    decode_attn_split with n_splits (None: the library's plan), a shorter one decode_attn."""
+    min_keys = DECODE_SPLIT_MIN_KEYS
+    n_splits = None
+
+    def __init__(self, previous):
+        self._previous = previous
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        _DecodeSplit.min_keys, _DecodeSplit.n_splits = self._previous
+        return False
+
+
+def decode_split(min_keys: int = DECODE_SPLIT_MIN_KEYS, n_splits: Optional[int] = None) -> _DecodeSplit:
+    """Set from how many keys on a decode step runs as split-key attention + merge, and with how many splits (None: the plan's
+    choice).  The default, 10241, is exactly where decode_attn raises, so no shorter history changes its route or its bits.  The
+    setting holds for the process; used as `with ops.decode_split(...):` the previous values come back on exit."""
+    assert min_keys >= 1 and (n_splits is None or 1 <= n_splits <= _lib.DECODE_MAX_SPLITS)
+    handle = _DecodeSplit((_DecodeSplit.min_keys, _DecodeSplit.n_splits))
+    _DecodeSplit.min_keys, _DecodeSplit.n_splits = int(min_keys), n_splits
+    return handle
+
+
+def decode_split_settings():
+    """(min_keys, n_splits) as ops.decode_split last set them."""
+    return _DecodeSplit.min_keys, _DecodeSplit.n_splits
+
+
+def decode_attn_split_plan(M: int, n_heads: int, n_kv_heads: int, head_dim: int, Sk: int):
+    """(n_splits, workspace bytes) licv_decode_attn_split chooses for M rows over Sk keys."""
+    n = C.c_int(0)
+    nbytes = _lib.lib().licv_decode_attn_split_plan(M, n_heads, n_kv_heads, head_dim, Sk, C.byref(n))
+    return n.value, int(nbytes)
+
+
+def decode_attn_split(qkv, cos: torch.Tensor, sin: torch.Tensor, position_ids: torch.Tensor, cache: torch.Tensor, past: int, n_heads: int,
+                      n_kv_heads: int, head_dim: int, scale: float, key_valid: Optional[torch.Tensor] = None,
+                      kv_rows: Optional[torch.Tensor] = None, n_splits: Optional[int] = None) -> torch.Tensor:
+    """decode_attn for a history of any length, in two launches (licv_decode_attn_split): the key range of every (row, kv head) is cut
+    into n_splits runs of 64-key sweeps (None: the library's plan; more than there are sweeps: clamped), each leaves an un-normalised
+    partial in a workspace allocated here, and a merge launch writes O.  Same arguments, same cache afterwards; one split gives
+    decode_attn's bits."""
+    a, out, M = _decode_attn_args(qkv, cos, sin, position_ids, cache, past, n_heads, n_kv_heads, head_dim, scale, key_valid, kv_rows)
+    Sk = int(past) + 1
+    if n_splits is None:
+        n, nbytes = decode_attn_split_plan(M, n_heads, n_kv_heads, head_dim, Sk)
+    else:
+        assert 1 <= n_splits <= _lib.DECODE_MAX_SPLITS, f"n_splits {n_splits}: 1 .. {_lib.DECODE_MAX_SPLITS}"
+        n = min(int(n_splits), (Sk + 63) // 64)
+        nbytes = M * n_heads * n * (head_dim + 2) * 4
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=cache.device)
+    check(_lib.lib().licv_decode_attn_split(C.byref(a), n, _p(ws), nbytes, _stream(cache)))
     return out
 
 

@@ -260,14 +260,16 @@ def _sampling_kwargs(do_sample, temperature, top_k, top_p, min_p, rest):
 
 class Idefics2Interface(IdeficsInterface):
     """Idefics2Interface(model_name_or_path, precision, device, prompt_manager, instruction, image_field, label_field)
-    (ref:utils.py:68-78).  Hook sites are the text layers' MLP branches (ref:config/lmm/idefics2-8B-base.yaml:8)."""
+    (ref:utils.py:68-78).  Hook sites are the text layers' MLP branches (ref:config/lmm/idefics2-8B-base.yaml:8).
+    max_positions (keyword only): length of the rotary table, the longest prompt + answer the engine accepts (a 32-shot prompt with
+    image splitting is about 11 k tokens; decode steps over more than 10 240 keys run as split-key attention, ops.decode_split)."""
     image_norm = ("IDEFICS2_MEAN", "IDEFICS2_STD")
 
     HOOK_SITE = re.compile(r"^model\.model\.text_model\.layers\.(\d+)\.mlp$")
 
     def __init__(self, model_name_or_path=None, precision="bf16", device="cuda", prompt_manager=None, instruction="",
                  image_field="image", label_field="answer", *, state_dict: Optional[Dict[str, torch.Tensor]] = None,
-                 arch: Optional[Idefics2Arch] = None, tokenizer=None, processor=None):
+                 arch: Optional[Idefics2Arch] = None, tokenizer=None, processor=None, max_positions: int = 4096):
         LMMInterface.__init__(self)
         if str(precision) not in ("bf16", "bfloat16", "torch.bfloat16"):
             raise ValueError(f"the native Idefics2 path computes in bf16 only (got precision={precision!r})")
@@ -275,7 +277,7 @@ class Idefics2Interface(IdeficsInterface):
             state_dict, arch, tokenizer, processor = self._load_checkpoint(Path(model_name_or_path), tokenizer, processor, Idefics2Arch)
         self.arch = arch
         self._device = torch.device(device)
-        self.engine = Idefics2Engine(Idefics2Weights(state_dict, arch, self._device))
+        self.engine = Idefics2Engine(Idefics2Weights(state_dict, arch, self._device, max_positions=max_positions))
         self.model = _NativeModel(arch, "idefics2")
         self.prompt_manager, self.instruction = prompt_manager, instruction
         self.image_field, self.label_field = image_field, label_field
