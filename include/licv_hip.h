@@ -30,7 +30,9 @@ extern "C" {
  * constrained decoding: licv_logits_process is a new symbol, and licv_beam_step accepts one new VALUE of an existing field
  * (logits_dtype = LICV_F32_LOGPROBS) that no earlier caller passes - no struct changed its layout; and still 9 with candidate ranking:
  * licv_append_attn is a new symbol with a struct of its own; and still 9 with decode steps over long histories:
- * licv_decode_attn_split_plan and licv_decode_attn_split are new symbols that take licv_decode_attn_args as it is. */
+ * licv_decode_attn_split_plan and licv_decode_attn_split are new symbols that take licv_decode_attn_args as it is; and still 9 with
+ * the text stack on packed rows: licv_attn_fwd_ragged and licv_idefics_text_forward_packed are new symbols that take licv_attn_args and
+ * licv_idefics_text_call as they are. */
 #define LICV_ABI_VERSION 9
 
 enum { LICV_BF16 = 0, LICV_F32 = 1 };
@@ -250,6 +252,16 @@ typedef struct {
 } licv_attn_args;
 
 int licv_attn_fwd(const licv_attn_args* a, void* stream);
+/* The same tiled kernel on PACKED rows, for right-padded batches whose padding rows are left out (mask modes 1 and 3 only): sequence b
+ * is rows cu_seqlens[b] .. cu_seqlens[b+1]-1 of Q and O (row strides q_rs and n_heads*hd; q_bs and Sq are ignored).  Mode 1: K and V
+ * are packed the same way (kv_rs; kv_bs and Sk ignored), every sequence is causal on its own rows (Sk_b = Sq_b), key_valid is ignored:
+ * under right padding a real query never sees a padding key.  Mode 3: K and V stay (B, Sk) per batch row (kv_bs, kv_rs), img_mask is
+ * packed (total, n_img).  Key tiles and query blocks keep their boundaries relative to the sequence start, so every real row gets the
+ * bits licv_attn_fwd gives it in the padded batch; rows past cu_seqlens[B] are not touched.  cu_seqlens: B + 1 int32, [0] = 0,
+ * ascending in steps >= 1, given twice as licv_attn_varlen_causal takes it (HOST pointer for the checks and the grid, device copy for
+ * the kernel, complete on `stream` before the call; a workgroup whose device offsets leave the packed rows does nothing).  A missing
+ * copy, cu_seqlens not ascending from 0, a length of 0 or another mask mode: LICV_E_BADARG, nothing launched. */
+int licv_attn_fwd_ragged(const licv_attn_args* a, const int32_t* cu_seqlens_host, const int32_t* cu_seqlens_dev, void* stream);
 /* tests / A-B timing: bit 0 = always the tiled kernel (never the resident-K/V variant used for short unmasked keys);
  * bit 1 = the resident variant walks its items in blockIdx order instead of grouping consecutive heads on one XCD;
  * bit 2 = the resident variant leaves its LDS read schedule to the compiler; bit 3 = so does the tiled kernel at head dim 128 */
@@ -366,6 +378,19 @@ typedef struct {
  * licv_append_attn also when S == 1), which may then hold fewer rows than B. */
 int licv_runner_option(int option, int value);
 int licv_idefics_text_forward(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, void* stream);
+/* The same forward for a RIGHT-PADDED batch (row b holds cu_seqlens[b+1] - cu_seqlens[b] real tokens, then padding) without the
+ * padding rows: the call is the one licv_idefics_text_forward takes - unpacked (B, S) inputs, scratch sized for M = B*S, unpacked
+ * logits, logits_rows addressing b*S + s - and kv_cache must be NULL.  One kernel gathers input_ids, position_ids, gate and the
+ * img_mask rows to packed order into pack_scratch (>= total * (20 + 4*n_img) bytes, 16-byte aligned, total = cu_seqlens[B]); every
+ * launch up to and including the final RMSNorm runs on `total` rows (both attentions through licv_attn_fwd_ragged); the normed rows
+ * are scattered back to (B*S, hidden) with zeros at padding positions, and the LM head / logits_rows gather run as ever.  Real
+ * positions get the bits of licv_idefics_text_forward wherever licv_gemm_splitk_plan answers the same split count for `total` rows as
+ * for B*S (the caller's gate); padding positions get logits of exactly 0.  pack_rows = 0 (the gate is closed): every launch runs on
+ * the B*S padded rows as in licv_idefics_text_forward (pack_scratch may be NULL) and only the padding rows of the final norm are
+ * zeroed, so the logits of a right-padded batch are the same at EVERY position whichever way the gate went.  cu_seqlens as
+ * licv_attn_fwd_ragged takes it, every length 1 .. S; otherwise LICV_E_BADARG and nothing launched. */
+int licv_idefics_text_forward_packed(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, const int32_t* cu_seqlens_host,
+                                     const int32_t* cu_seqlens_dev, int pack_rows, void* pack_scratch, int64_t pack_scratch_bytes, void* stream);
 
 /* ---- one decode step's self-attention block (ref:inference.py:300-321: B x num_beams rows, one new token each; hf eager attention
  * hf:idefics/modeling_idefics.py:450-470, rotary :396-428, hf:mistral/modeling_mistral.py:122-179 for GQA) in ONE launch: fused QKV rows

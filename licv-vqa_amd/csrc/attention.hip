@@ -33,6 +33,7 @@ struct AttnP {
     int mask_mode;
     const int32_t* key_valid;
     const int32_t* img_mask; int n_img, img_len;
+    const int32_t* cu; int total;      // ragged form (licv_attn_fwd_ragged): B + 1 packed row offsets and their end, else NULL
 };
 
 // LDS row stride (bytes) for a tile with `cols` bf16 columns: the smallest 16-byte multiple >= the row whose dword
@@ -309,7 +310,21 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
     const int b = pair / a.nh;
     const int kvh = head / (a.nh / a.nkv);
     const int q0 = qt * QBLK;
-    const int coff = a.Sk - a.Sq;                          // causal offset (decode steps: Sq < Sk)
+    // Ragged form: sequence b is the packed rows cu[b] .. cu[b+1]-1 of Q and O (mode 1: of K and V too, Sk = Sq = its length; mode 3:
+    // of img_mask, K / V stay per batch row).  The grid is sized for the longest sequence (a.Sq); everything below runs on this
+    // sequence's own lengths, all of them wave-uniform (SGPRs), so tiles and rounding points are those of a dense call on (len, len).
+    int Sq = a.Sq, Sk = a.Sk;
+    int64_t qbase = (int64_t)b * a.q_bs, kvbase = (int64_t)b * a.kv_bs, orow0 = (int64_t)b * a.Sq;
+    if (a.cu) {
+        const int s0 = a.cu[b];
+        Sq = a.cu[b + 1] - s0;
+        // a query block past this sequence's end: nothing loaded, nothing written (nor for offsets that leave the packed rows:
+        // a device copy that disagrees with the host's validated one)
+        if (q0 >= Sq || s0 < 0 || s0 + Sq > a.total) return;
+        qbase = (int64_t)s0 * a.q_rs; orow0 = s0;
+        if (MODE == 1) { Sk = Sq; kvbase = (int64_t)s0 * a.kv_rs; }
+    }
+    const int coff = Sk - Sq;                              // causal offset (decode steps: Sq < Sk)
     const float sc = a.scale * 1.4426950408889634f;        // softmax runs on exp2
 
     // ---- Q fragments (B operand of S^T = K.Q^T): Q[qrow][ks*32 + 8g .. +7]; sub-tile qs covers rows
@@ -318,18 +333,18 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
 #pragma unroll
     for (int qs = 0; qs < QT; ++qs) {
         const int qrow = q0 + qs * SLAB + wave * 16 + ql;
-        const bf16_t* qp = a.q + (int64_t)b * a.q_bs + (int64_t)qrow * a.q_rs + (int64_t)head * a.hd;
+        const bf16_t* qp = a.q + qbase + (int64_t)qrow * a.q_rs + (int64_t)head * a.hd;
 #pragma unroll
         for (int ks = 0; ks < DPK / 32; ++ks) {
             const int d = ks * 32 + g * 8;
             u32x4 r = u32x4{0u, 0u, 0u, 0u};
-            if (qrow < a.Sq && d < a.hd) r = *reinterpret_cast<const u32x4*>(qp + d);
+            if (qrow < Sq && d < a.hd) r = *reinterpret_cast<const u32x4*>(qp + d);
             qf[qs][ks] = *reinterpret_cast<bf16x8*>(&r);
         }
     }
 
-    int kend = a.Sk;
-    if (MODE == 1) kend = min(a.Sk, min(q0 + QBLK, a.Sq) + coff);   // keys beyond the last query's diagonal
+    int kend = Sk;
+    if (MODE == 1) kend = min(Sk, min(q0 + QBLK, Sq) + coff);   // keys beyond the last query's diagonal
     const int ntiles = (kend + ATT_KB - 1) / ATT_KB;
 
     // image-mask mode with whole tiles inside one image: a tile is visited only if some query of this
@@ -342,9 +357,9 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
 #pragma unroll
         for (int qs = 0; qs < QT; ++qs) {
             const int qrow = q0 + qs * SLAB + wave * 16 + ql;
-            const int32_t* imrow = a.img_mask + ((int64_t)b * a.Sq + qrow) * a.n_img;
+            const int32_t* imrow = a.img_mask + (orow0 + qrow) * a.n_img;
             for (int n = 0; n < a.n_img; ++n) {
-                const bool hit = qrow < a.Sq && imrow[n] != 0;
+                const bool hit = qrow < Sq && imrow[n] != 0;
                 if (__any(hit)) mine |= 1ull << n;
             }
         }
@@ -361,10 +376,10 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
     // column >= hd, thread past the tile) gets an out-of-range offset and comes back as zeros.  With the loads inside `if`s the
     // compiler's waitcnt pass waited for them (vmcnt(0)) at the first LDS-dependent instruction of the tile being multiplied:
     // the prefetch was synchronous.  (When fits32 is false - a (batch, head) slice beyond 2 GB - the host does not launch this kernel.)
-    const auto rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.k + (int64_t)b * a.kv_bs + (int64_t)kvh * a.hd), 0, 0xFFFFFFFF, 0x00020000);
-    const auto rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.v + (int64_t)b * a.kv_bs + (int64_t)kvh * a.hd), 0, 0xFFFFFFFF, 0x00020000);
+    const auto rsk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.k + kvbase + (int64_t)kvh * a.hd), 0, 0xFFFFFFFF, 0x00020000);
+    const auto rsv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(a.v + kvbase + (int64_t)kvh * a.hd), 0, 0xFFFFFFFF, 0x00020000);
     const bool use_kv = a.key_valid && (MODE == 1 || MODE == 2);
-    const auto rsf = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(use_kv ? a.key_valid + (int64_t)b * a.Sk : (const int32_t*)a.k), 0, 0xFFFFFFFF, 0x00020000);
+    const auto rsf = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(use_kv ? a.key_valid + (int64_t)b * Sk : (const int32_t*)a.k), 0, 0xFFFFFFFF, 0x00020000);
     constexpr uint32_t OOB = 0xFFFFFFFFu;
     u32x4 rk[KLD], rv[VLD];
     int rvalid = 1;
@@ -374,19 +389,19 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
         for (int i = 0; i < KLD; ++i) {
             const int c = tid + i * NTHR;
             const int row = c / KCH, ch = c % KCH;
-            const bool ok = (int)(c < ATT_KB * KCH) & (int)(key0 + row < a.Sk) & (int)(ch * 8 < a.hd);
+            const bool ok = (int)(c < ATT_KB * KCH) & (int)(key0 + row < Sk) & (int)(ch * 8 < a.hd);
             rk[i] = __builtin_amdgcn_raw_buffer_load_b128(rsk, ok ? (uint32_t)((key0 + row) * (int)a.kv_rs + ch * 8) * 2u : OOB, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < VLD; ++i) {
             const int c = tid + i * NTHR;
             const int row = c / VCH, ch = c % VCH;
-            const bool ok = (int)(c < ATT_KB * VCH) & (int)(key0 + row < a.Sk) & (int)(ch * 8 < a.hd);
+            const bool ok = (int)(c < ATT_KB * VCH) & (int)(key0 + row < Sk) & (int)(ch * 8 < a.hd);
             rv[i] = __builtin_amdgcn_raw_buffer_load_b128(rsv, ok ? (uint32_t)((key0 + row) * (int)a.kv_rs + ch * 8) * 2u : OOB, 0, 0);
         }
         {
             const int key = key0 + tid;
-            const bool in = (int)(tid < ATT_KB) & (int)(key < a.Sk);
+            const bool in = (int)(tid < ATT_KB) & (int)(key < Sk);
             const int f = __builtin_amdgcn_raw_buffer_load_b32(rsf, (in && use_kv) ? (uint32_t)key * 4u : OOB, 0, 0);
             rvalid = in ? (use_kv ? (f != 0) : 1) : 0;
         }
@@ -426,18 +441,18 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
         const int tn = next_tile(t + 1);
         if (tn < ntiles) load_tile(tn);
         const int key0 = t * ATT_KB;
-        const int nst = min(4, (min(a.Sk, kend) - key0 + 15) >> 4);      // 16-key sub-tiles that hold real keys
+        const int nst = min(4, (min(Sk, kend) - key0 + 15) >> 4);      // 16-key sub-tiles that hold real keys
         const bool tile_all_valid = sAllValid != 0;
 
 #pragma unroll
         for (int qs = 0; qs < QT; ++qs) {
             const int qw0 = q0 + qs * SLAB + wave * 16;          // first query of this wave's sub-tile (wave-uniform)
-            if (qw0 >= a.Sq) continue;                              // sub-tile past the last query: only helps loading
+            if (qw0 >= Sq) continue;                              // sub-tile past the last query: only helps loading
             if (MODE == 1 && key0 > qw0 + 15 + coff) continue;   // tile entirely in this sub-tile's future
             const int qrow = qw0 + ql;
-            const bool qok = qrow < a.Sq;
-            const int32_t* imrow = (MODE == 3 && qok) ? a.img_mask + ((int64_t)b * a.Sq + qrow) * a.n_img : nullptr;
-            bool need_mask = (key0 + ATT_KB > a.Sk) || (qw0 + 16 > a.Sq) || !tile_all_valid;
+            const bool qok = qrow < Sq;
+            const int32_t* imrow = (MODE == 3 && qok) ? a.img_mask + (orow0 + qrow) * a.n_img : nullptr;
+            bool need_mask = (key0 + ATT_KB > Sk) || (qw0 + 16 > Sq) || !tile_all_valid;
             if (MODE == 1) need_mask = need_mask || (key0 + ATT_KB - 1 > qw0 + coff);
             if (MODE == 3) need_mask = true;
             const int img_ok_tile = (img_uniform && imrow) ? (imrow[key0 / a.img_len] != 0) : 0;
@@ -486,8 +501,8 @@ void attn_fwd_k(AttnP a) {                    // PIPE: full tiles through attn_t
         l += __shfl_xor(l, 16, 64);
         l += __shfl_xor(l, 32, 64);
         const float inv = l > 0.f ? 1.0f / l : 0.f;
-        if (qrow < a.Sq) {
-            bf16_t* op = a.o + ((int64_t)b * a.Sq + qrow) * ((int64_t)a.nh * a.hd) + (int64_t)head * a.hd;
+        if (qrow < Sq) {
+            bf16_t* op = a.o + (orow0 + qrow) * ((int64_t)a.nh * a.hd) + (int64_t)head * a.hd;
 #pragma unroll
             for (int dt = 0; dt < DPV / 16; ++dt) {
                 const int d = dt * 16 + g * 4;
@@ -878,6 +893,7 @@ extern "C" int licv_attn_fwd(const licv_attn_args* x, void* stream) {
     p.B = (int)x->B; p.Sq = (int)x->Sq; p.Sk = (int)x->Sk; p.nh = (int)x->n_heads; p.nkv = (int)x->n_kv_heads; p.hd = (int)x->head_dim;
     p.scale = x->scale; p.mask_mode = x->mask_mode; p.key_valid = x->key_valid;
     p.img_mask = x->img_mask; p.n_img = (int)x->n_img; p.img_len = (int)x->img_len;
+    p.cu = nullptr; p.total = 0;
     const int hd0 = (int)x->head_dim;
     // (Sq >= 128: with fewer than 8 sub-tiles of 16 queries some of the 8 waves idle — the perceiver's 64 latents run
     //  1.4x faster on the tiled kernel)
@@ -963,6 +979,56 @@ extern "C" int licv_attn_fwd(const licv_attn_args* x, void* stream) {
         case 1:  if (DK == 128 && !g_attn_tiled_no_pipe) attn_fwd_k<DK, DV, 1, 4, 1, DK == 128><<<grid, block, 0, st>>>(p); else attn_fwd_k<DK, DV, 1, 4, 1><<<grid, block, 0, st>>>(p); break; \
         case 2:  if (DK == 128 && !g_attn_tiled_no_pipe) attn_fwd_k<DK, DV, 1, 4, 2, DK == 128><<<grid, block, 0, st>>>(p); else attn_fwd_k<DK, DV, 1, 4, 2><<<grid, block, 0, st>>>(p); break; \
         default: attn_fwd_k<DK, DV, 1, 4, 3><<<grid, block, 0, st>>>(p); break; } } while (0)
+    if (hd <= 16)        ATT_LAUNCH(32, 16);
+    else if (hd <= 32)   ATT_LAUNCH(32, 32);
+    else if (hd <= 64)   ATT_LAUNCH(64, 64);
+    else if (hd <= 80)   ATT_LAUNCH(96, 80);
+    else if (hd <= 96)   ATT_LAUNCH(96, 96);
+    else                 ATT_LAUNCH(128, 128);
+#undef ATT_LAUNCH
+    LICV_LAUNCH_CHECK();
+    return LICV_OK;
+}
+
+// Ragged form of the tiled kernel for right-padded batches run on packed rows (mask modes 1 and 3): the same instantiations as
+// licv_attn_fwd launches, with the per-sequence offset and length read from cu_seqlens by each workgroup.
+extern "C" int licv_attn_fwd_ragged(const licv_attn_args* x, const int32_t* cu_seqlens_host, const int32_t* cu_seqlens_dev, void* stream) {
+    LICV_CHECK_ARG(x && x->q && x->k && x->v && x->o, "attn_fwd_ragged: null pointer");
+    LICV_CHECK_ARG(cu_seqlens_host && cu_seqlens_dev, "attn_fwd_ragged: cu_seqlens must be given twice (host and device copy)");
+    LICV_CHECK_ARG(x->mask_mode == 1 || x->mask_mode == 3, "attn_fwd_ragged: mask mode %d (only 1 = causal and 3 = image mask)", x->mask_mode);
+    LICV_CHECK_ARG(x->B > 0 && x->B < (1ll << 20) && x->n_heads > 0 && x->n_kv_heads > 0, "attn_fwd_ragged: bad shape");
+    LICV_CHECK_ARG(x->n_heads % x->n_kv_heads == 0, "attn_fwd_ragged: n_heads must be a multiple of n_kv_heads");
+    LICV_CHECK_ARG(x->head_dim % 8 == 0 && x->head_dim >= 8 && x->head_dim <= 128, "attn_fwd_ragged: head_dim %lld unsupported (multiple of 8, <= 128)", (long long)x->head_dim);
+    LICV_CHECK_ARG(x->q_rs % 8 == 0 && x->kv_rs % 8 == 0 && x->kv_bs % 8 == 0, "attn_fwd_ragged: strides must be multiples of 8 elements");
+    LICV_CHECK_ARG(((uintptr_t)x->q & 15) == 0 && ((uintptr_t)x->k & 15) == 0 && ((uintptr_t)x->v & 15) == 0 && ((uintptr_t)x->o & 7) == 0, "attn_fwd_ragged: misaligned pointer");
+    LICV_CHECK_ARG(cu_seqlens_host[0] == 0, "attn_fwd_ragged: cu_seqlens[0] = %d, must be 0", (int)cu_seqlens_host[0]);
+    int64_t max_len = 0;
+    for (int64_t i = 0; i < x->B; ++i) {
+        const int64_t len = (int64_t)cu_seqlens_host[i + 1] - (int64_t)cu_seqlens_host[i];
+        LICV_CHECK_ARG(len >= 1, "attn_fwd_ragged: sequence %lld has length %lld (cu_seqlens must ascend in steps of at least 1)", (long long)i, (long long)len);
+        if (len > max_len) max_len = len;
+    }
+    const int64_t Sk = x->mask_mode == 1 ? max_len : x->Sk;
+    LICV_CHECK_ARG(Sk > 0 && max_len < (1ll << 30) && Sk < (1ll << 30), "attn_fwd_ragged: bad key count / sequence too long");
+    LICV_CHECK_ARG(x->mask_mode != 3 || (x->img_mask && x->n_img > 0 && x->img_len > 0 && x->n_img * x->img_len >= x->Sk), "attn_fwd_ragged: image mask arguments inconsistent");
+    LICV_CHECK_ARG(Sk * x->kv_rs * 2 < (1ll << 32) && Sk * 4 < (1ll << 32), "attn_fwd_ragged: one (sequence, head) slice of K / V spans more than 4 GB");
+    AttnP p;
+    p.q = (const bf16_t*)x->q; p.q_bs = 0; p.q_rs = x->q_rs;
+    p.k = (const bf16_t*)x->k; p.v = (const bf16_t*)x->v; p.kv_bs = x->mask_mode == 1 ? 0 : x->kv_bs; p.kv_rs = x->kv_rs;
+    p.o = (bf16_t*)x->o;
+    p.B = (int)x->B; p.Sq = (int)max_len; p.Sk = (int)Sk; p.nh = (int)x->n_heads; p.nkv = (int)x->n_kv_heads; p.hd = (int)x->head_dim;
+    p.scale = x->scale; p.mask_mode = x->mask_mode; p.key_valid = nullptr;       // right padding under the causal mask: no real query sees a padding key
+    p.img_mask = x->img_mask; p.n_img = (int)x->n_img; p.img_len = (int)x->img_len;
+    p.cu = cu_seqlens_dev; p.total = cu_seqlens_host[x->B];
+    const int hd = p.hd;
+    const int64_t qtiles = (max_len + ATT_QB - 1) / ATT_QB;        // the grid of the longest sequence; shorter ones return early
+    const int64_t nblk = x->B * x->n_heads * qtiles;
+    LICV_CHECK_ARG(nblk < (1ll << 31), "attn_fwd_ragged: grid too large");
+    const dim3 grid((unsigned)nblk), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define ATT_LAUNCH(DK, DV) do { if (p.mask_mode == 3) attn_fwd_k<DK, DV, 1, 4, 3><<<grid, block, 0, st>>>(p); \
+        else if (DK == 128 && !g_attn_tiled_no_pipe) attn_fwd_k<DK, DV, 1, 4, 1, DK == 128><<<grid, block, 0, st>>>(p); \
+        else attn_fwd_k<DK, DV, 1, 4, 1><<<grid, block, 0, st>>>(p); } while (0)
     if (hd <= 16)        ATT_LAUNCH(32, 16);
     else if (hd <= 32)   ATT_LAUNCH(32, 32);
     else if (hd <= 64)   ATT_LAUNCH(64, 64);

@@ -125,7 +125,42 @@ extern "C" int licv_runner_option(int option, int value) {
     return licv_set_error(LICV_E_BADARG, "runner_option: unknown option %d", option);
 }
 
-extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, void* stream) {
+namespace {
+// Packed rows (licv_idefics_text_forward_packed): the right-padded (B, S) batch runs as `total` real rows, sequence b on rows
+// cu[b] .. cu[b+1]-1, up to and including the final RMSNorm; the per-row inputs below are the call's, gathered to that order.
+// Either way the padding rows enter the LM head as zeros, so what a caller gets does not depend on whether the rows were packed.
+struct Pack {
+    bool packed;                                          // false: the stack runs on the padded rows; only the padding rows of the final norm are zeroed
+    const int32_t* cu_host; const int32_t* cu_dev; int64_t total;
+    const int64_t* input_ids; const int64_t* position_ids; const float* gate; const int32_t* img_mask;
+};
+
+// one thread per packed row: its (b, s) from cu, then the row's id, position, gate and image-mask row
+__global__ __launch_bounds__(256)
+void pack_inputs_k(const int32_t* __restrict__ cu, int B, int64_t S, int n_img, int64_t total, const int64_t* __restrict__ ids,
+                   const int64_t* __restrict__ pos, const float* __restrict__ gate, const int32_t* __restrict__ img_mask,
+                   int64_t* __restrict__ ids_o, int64_t* __restrict__ pos_o, float* __restrict__ gate_o, int32_t* __restrict__ img_o) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= total) return;
+    int b = 0;
+    while (b + 1 < B && (int64_t)cu[b + 1] <= r) ++b;
+    const int64_t s = r - cu[b];
+    const bool ok = s >= 0 && s < S;                      // (always, for the cu the host validated)
+    const int64_t src = (int64_t)b * S + (ok ? s : 0);
+    ids_o[r] = ok ? ids[src] : 0; pos_o[r] = ok ? pos[src] : 0; gate_o[r] = ok ? gate[src] : 0.f;
+    for (int n = 0; n < n_img; ++n) img_o[r * n_img + n] = ok ? img_mask[src * n_img + n] : 0;
+}
+
+// one workgroup per row of the unpacked (B * S, H) buffer: its source row (the packed one, or itself), or zeros at a padding position
+__global__ __launch_bounds__(256)
+void unpack_rows_k(const int32_t* __restrict__ cu, int64_t S, int64_t total, int64_t chunks, int packed, const uint4* __restrict__ src, uint4* __restrict__ dst) {
+    const int64_t row = blockIdx.x, b = row / S, s = row % S;
+    const int64_t s0 = cu[b], r = packed ? s0 + s : row;
+    const bool real = s0 >= 0 && s < (int64_t)cu[b + 1] - s0 && (!packed || r < total);
+    for (int64_t i = threadIdx.x; i < chunks; i += 256) dst[row * chunks + i] = real ? src[r * chunks + i] : uint4{0u, 0u, 0u, 0u};
+}
+
+int text_forward(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, void* stream, const Pack* pk) {
     LICV_CHECK_ARG(w && c, "idefics_text_forward: null argument");
     LICV_CHECK_ARG(w->dec && w->embed && w->final_ln && w->lm_head && w->cos && w->sin, "idefics_text_forward: missing weights");
     LICV_CHECK_ARG(c->input_ids && c->key_valid && c->position_ids && c->image_states && c->img_mask && c->gate, "idefics_text_forward: missing inputs");
@@ -135,7 +170,12 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
     LICV_CHECK_ARG(c->kv_cache || c->Sk == c->S, "idefics_text_forward: without a KV cache the mask must span exactly the new tokens");
     LICV_CHECK_ARG(c->xkv_cached || c->xkv, "idefics_text_forward: no cross-attention K/V cache and no scratch to project into");
     const int64_t H = w->hidden, I = w->inter, nh = w->n_heads, hd = w->head_dim, E = w->img_dim;
-    const int64_t B = c->B, S = c->S, M = B * S, Nk = c->Nk;
+    const bool packed = pk && pk->packed;
+    const int64_t B = c->B, S = c->S, M = packed ? pk->total : B * S, Nk = c->Nk;
+    const int64_t* input_ids = packed ? pk->input_ids : c->input_ids;
+    const int64_t* position_ids = packed ? pk->position_ids : c->position_ids;
+    const float* gate = packed ? pk->gate : c->gate;
+    const int32_t* img_mask = packed ? pk->img_mask : c->img_mask;
     const float att_scale = 1.0f / sqrtf((float)hd);
     hipStream_t st = (hipStream_t)stream;
     Ctx x{w, c, stream, M, H, c->h16, LICV_BF16};
@@ -165,7 +205,7 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
         f.active = f.side && f.ev.size() >= f.plan.size();
     }
 
-    RUN(licv_embed_gather(c->input_ids, w->embed, w->embed_extra, c->h16, M, H, w->vocab, w->n_extra_vocab, stream));
+    RUN(licv_embed_gather(input_ids, w->embed, w->embed_extra, c->h16, M, H, w->vocab, w->n_extra_vocab, stream));
     bool xn_valid = false;                                 // c->xn holds RMSNorm(h) for the next block (made by the fused hook kernel)
     bool pending = false; float pending_scale = 0.f;       // a cross layer's MLP branch waits in c->q (or as split-K slices) for the next norm to add it
     Slices pending_src;
@@ -194,18 +234,19 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
             a.q = c->q; a.q_bs = S * H; a.q_rs = H;
             a.k = kv; a.v = (const char*)kv + H * 2; a.kv_bs = Nk * 2 * H; a.kv_rs = 2 * H;
             a.o = c->o; a.B = B; a.Sq = S; a.Sk = Nk; a.n_heads = nh; a.n_kv_heads = nh; a.head_dim = hd;
-            a.scale = att_scale; a.mask_mode = 3; a.key_valid = nullptr; a.img_mask = c->img_mask; a.n_img = c->n_img; a.img_len = w->img_len;
-            RUN(licv_attn_fwd(&a, stream));
+            a.scale = att_scale; a.mask_mode = 3; a.key_valid = nullptr; a.img_mask = img_mask; a.n_img = c->n_img; a.img_len = w->img_len;
+            if (packed) RUN(licv_attn_fwd_ragged(&a, pk->cu_host, pk->cu_dev, stream));
+            else RUN(licv_attn_fwd(&a, stream));
             if (g_fold_residual) {                         // both gated residual adds folded into the norms that follow (see below)
                 Slices os;
                 RUN(linear_to_rows(x, c->o, M, X.o_w, H, H, c->q, &os));
-                if (os.ws) RUN(licv_add_rmsnorm_fwd_ws(x.h, x.h_dt, os.ws, os.splits, os.slice, os.stride, c->gate, 1, X.gate_attn, X.post_ln, c->x, M, H, w->rms_eps, 0, stream));
-                else RUN(licv_add_rmsnorm_fwd(x.h, x.h_dt, c->q, c->gate, 1, X.gate_attn, X.post_ln, c->x, M, H, w->rms_eps, 0, stream));
+                if (os.ws) RUN(licv_add_rmsnorm_fwd_ws(x.h, x.h_dt, os.ws, os.splits, os.slice, os.stride, gate, 1, X.gate_attn, X.post_ln, c->x, M, H, w->rms_eps, 0, stream));
+                else RUN(licv_add_rmsnorm_fwd(x.h, x.h_dt, c->q, gate, 1, X.gate_attn, X.post_ln, c->x, M, H, w->rms_eps, 0, stream));
                 RUN(linear(x, c->x, M, X.gu_w, 2 * I, H, c->act, I, LICV_BF16, nullptr, 0, nullptr, nullptr, 1));
                 RUN(linear_to_rows(x, c->act, M, X.down_w, H, I, c->q, &pending_src));
                 pending_scale = X.gate_dense; pending = true;     // added by the decoder layer's input norm
             } else {
-                RUN(linear(x, c->o, M, X.o_w, H, H, x.h, H, x.h_dt, x.h, x.h_dt, c->gate, &X.gate_attn));
+                RUN(linear(x, c->o, M, X.o_w, H, H, x.h, H, x.h_dt, x.h, x.h_dt, gate, &X.gate_attn));
                 RUN(licv_rmsnorm_fwd(x.h, x.h_dt, X.post_ln, c->x, M, H, 1, H, H, w->rms_eps, 0, stream));
                 RUN(linear(x, c->x, M, X.gu_w, 2 * I, H, c->act, I, LICV_BF16, nullptr, 0, nullptr, nullptr, 1));
                 RUN(linear(x, c->act, M, X.down_w, H, I, x.h, H, x.h_dt, x.h, x.h_dt, nullptr, &X.gate_dense));
@@ -225,7 +266,7 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
         const bool continuation = c->kv_cache && c->kv_rows && (S > 1 || !g_append_continuation);
         if (c->kv_cache && M < 512 && !continuation) RUN(linear_to_rows(x, xin, M, D.qkv_w, 3 * H, H, c->qkv, &qs));
         else RUN(linear(x, xin, M, D.qkv_w, 3 * H, H, c->qkv, 3 * H, LICV_BF16));
-        if (!c->kv_cache) RUN(licv_rotary_fwd(c->qkv, w->cos, w->sin, c->position_ids, M, nh, hd, 3 * H, H, 2, w->rope_len, stream));
+        if (!c->kv_cache) RUN(licv_rotary_fwd(c->qkv, w->cos, w->sin, position_ids, M, nh, hd, 3 * H, H, 2, w->rope_len, stream));
         licv_attn_args a;
         a.q = c->qkv; a.q_bs = S * 3 * H; a.q_rs = 3 * H;
         a.o = c->o; a.B = B; a.Sq = S; a.n_heads = nh; a.n_kv_heads = nh; a.head_dim = hd; a.scale = att_scale; a.mask_mode = 1;
@@ -261,7 +302,8 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
             else RUN(licv_rotary_kv_append(c->qkv, w->cos, w->sin, c->position_ids, B, S, nh, hd, w->rope_len, cache, c->cache_max_len, c->past, stream));
             a.k = cache; a.v = (const char*)cache + H * 2; a.kv_bs = c->cache_max_len * 2 * H; a.kv_rs = 2 * H; a.Sk = c->Sk;
         }
-        RUN(licv_attn_fwd(&a, stream));
+        if (packed) RUN(licv_attn_fwd_ragged(&a, pk->cu_host, pk->cu_dev, stream));
+        else RUN(licv_attn_fwd(&a, stream));
         }
         const int slot = (c->hook_slot && c->icv) ? c->hook_slot[l] : -1;
         // Large batches (the 256-tile GEMMs): the two residual adds of the layer leave the GEMM epilogues — a read-modify-write of the
@@ -302,12 +344,54 @@ extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, con
     const void* xf = c->xn;
     if (!xn_valid) { RUN(licv_rmsnorm_fwd(x.h, x.h_dt, w->final_ln, c->x, M, H, 1, H, H, w->rms_eps, 0, stream)); xf = c->x; }
     int64_t rows = M;
+    if (pk) {
+        // back to the (B * S, H) layout the LM head and logits_rows address: c->q is free here; padding rows are zeros (so are their logits)
+        unpack_rows_k<<<dim3((unsigned)(B * S)), dim3(256), 0, st>>>(pk->cu_dev, S, pk->total, H / 8, packed ? 1 : 0, (const uint4*)xf, (uint4*)c->q);
+        LICV_LAUNCH_CHECK();
+        xf = c->q; rows = B * S;
+    }
     if (c->logits_rows && c->n_rows > 0) {
         LICV_CHECK_ARG(c->xsel, "idefics_text_forward: logits_rows given without the xsel scratch");
-        RUN(licv_embed_gather(c->logits_rows, xf, nullptr, c->xsel, c->n_rows, H, M, 0, stream));
+        RUN(licv_embed_gather(c->logits_rows, xf, nullptr, c->xsel, c->n_rows, H, rows, 0, stream));
         xf = c->xsel; rows = c->n_rows;
     }
     const int rc_head = linear(x, xf, rows, w->lm_head, w->vocab_total, H, c->logits, c->ld_logits, LICV_BF16);
     g_pf.active = false;
     return rc_head;
+}
+}  // namespace
+
+extern "C" int licv_idefics_text_forward(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, void* stream) {
+    return text_forward(w, c, stream, nullptr);
+}
+
+extern "C" int licv_idefics_text_forward_packed(const licv_idefics_text_weights* w, const licv_idefics_text_call* c, const int32_t* cu_seqlens_host,
+                                                const int32_t* cu_seqlens_dev, int pack_rows, void* pack_scratch, int64_t pack_scratch_bytes, void* stream) {
+    LICV_CHECK_ARG(w && c && cu_seqlens_host && cu_seqlens_dev && (pack_scratch || !pack_rows), "idefics_text_forward_packed: null argument");
+    LICV_CHECK_ARG(!c->kv_cache, "idefics_text_forward_packed: packed rows run without a KV cache only");
+    LICV_CHECK_ARG(c->input_ids && c->position_ids && c->img_mask && c->gate && c->q, "idefics_text_forward_packed: missing inputs");
+    LICV_CHECK_ARG(c->B > 0 && c->B < (1ll << 20) && c->S > 0 && c->Sk == c->S && c->n_img > 0 && c->B * c->S < (1ll << 31), "idefics_text_forward_packed: bad shape");
+    LICV_CHECK_ARG(w->hidden % 8 == 0, "idefics_text_forward_packed: hidden size must be a multiple of 8");
+    LICV_CHECK_ARG(cu_seqlens_host[0] == 0, "idefics_text_forward_packed: cu_seqlens[0] = %d, must be 0", (int)cu_seqlens_host[0]);
+    for (int64_t b = 0; b < c->B; ++b) {
+        const int64_t len = (int64_t)cu_seqlens_host[b + 1] - (int64_t)cu_seqlens_host[b];
+        LICV_CHECK_ARG(len >= 1 && len <= c->S, "idefics_text_forward_packed: sequence %lld has length %lld (1 .. S = %lld)", (long long)b, (long long)len, (long long)c->S);
+    }
+    const int64_t total = cu_seqlens_host[c->B], n_img = c->n_img;
+    if (!pack_rows) {                                      // padded rows, zeros at the padding positions all the same
+        const Pack pk{false, cu_seqlens_host, cu_seqlens_dev, total, nullptr, nullptr, nullptr, nullptr};
+        return text_forward(w, c, stream, &pk);
+    }
+    const int64_t need = total * (8 + 8 + 4 + 4 * n_img);
+    LICV_CHECK_ARG(pack_scratch_bytes >= need && ((uintptr_t)pack_scratch & 15) == 0, "idefics_text_forward_packed: pack_scratch of %lld B (16-byte aligned) needed, %lld B given",
+                   (long long)need, (long long)pack_scratch_bytes);
+    int64_t* ids = (int64_t*)pack_scratch;
+    int64_t* pos = ids + total;
+    float* gate = (float*)(pos + total);
+    int32_t* img = (int32_t*)(gate + total);
+    pack_inputs_k<<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(cu_seqlens_dev, (int)c->B, c->S, (int)n_img, total, c->input_ids,
+                                                                                                c->position_ids, c->gate, c->img_mask, ids, pos, gate, img);
+    LICV_LAUNCH_CHECK();
+    const Pack pk{true, cu_seqlens_host, cu_seqlens_dev, total, ids, pos, gate, img};
+    return text_forward(w, c, stream, &pk);
 }

@@ -172,6 +172,7 @@ def lib() -> C.CDLL:
             "licv_gemm_debug_timestamps": [P],
             "licv_attn_select": [I],
             "licv_attn_fwd": [C.POINTER(AttnArgs), P],
+            "licv_attn_fwd_ragged": [C.POINTER(AttnArgs), P, P, P],
             "licv_beam_step": [C.POINTER(BeamStepArgs), P],
             "licv_logits_process": [C.POINTER(LogitsProcessArgs), P],
             "licv_sample_step": [C.POINTER(SampleStepArgs), C.POINTER(SampleParams), P],

@@ -15,6 +15,7 @@ Data layout in HBM (all row-major, tokens flattened to M = B*S rows):
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
@@ -154,6 +155,37 @@ class KVCache:
         self.rows = rows
 
 
+class RowLengths:
+    """The rows' real-token counts of one forward, for running a right-padded batch on packed rows: ONE device-to-host read, queued
+    on the caller's stream before the batch is cut in slices (a copy into pinned memory and an event), and waited for only where a
+    slice needs the answer - behind the launches of its vision tower, so the device has work while the host waits.  The device
+    copy of cu_seqlens is made on the device: no host-to-device copy (from pageable memory it would wait for the slice's stream)."""
+
+    def __init__(self, attention_mask: torch.Tensor):
+        m = attention_mask != 0
+        n = m.sum(-1)
+        S = m.shape[1]
+        prefix = (m == (torch.arange(S, device=m.device)[None, :] < n[:, None])).all() & (n > 0).all()     # right padding, no empty row
+        self.cu = torch.cat([n.new_zeros(1), n.cumsum(0)]).to(torch.int32)
+        info = torch.cat([n, prefix.reshape(1).to(n.dtype)])
+        self._host = torch.empty(info.shape, dtype=info.dtype, pin_memory=True)
+        self._host.copy_(info, non_blocking=True)
+        self._event = torch.cuda.Event()
+        self._event.record()
+        self._lens, self._read = None, False
+
+    def lens(self, lo: int, hi: int):
+        """Lengths of rows lo .. hi-1, or None when some mask row is not a prefix of ones."""
+        if not self._read:
+            self._event.synchronize()
+            info = self._host.tolist()
+            self._lens, self._read = (info[:-1] if info[-1] else None), True
+        return None if self._lens is None else self._lens[lo:hi]
+
+    def cu_dev(self, lo: int, hi: int) -> torch.Tensor:
+        return (self.cu[lo:hi + 1] - self.cu[lo:lo + 1]).contiguous()
+
+
 class IdeficsEngine:
     def __init__(self, weights: IdeficsWeights, fuse_hook_norm: bool = True, use_runner: bool = True):
         self.w, self.arch = weights, weights.arch
@@ -168,9 +200,14 @@ class IdeficsEngine:
         # Measured at the headline shape: 222.9 -> 213.8 ms with 2 slices (3 / 4 slices: slower).  0 / 1 = off.
         self.batch_streams = 2
         self._side_streams = []
+        # A right-padded batch runs its language stack on the real rows only (licv_idefics_text_forward_packed) where that drops a
+        # whole 256-row GEMM tile per slice and keeps every projection's split-K plan (ops.pack_rows_plan): same bits at real
+        # positions, zeros at padding positions.  False (or LICV_PACK_ROWS=0 in the environment) = always padded, for A/B timing
+        # (the lengths are still read and the padding positions still zeroed: the logits do not depend on this switch).
+        self.pack_rows = os.environ.get("LICV_PACK_ROWS", "1") != "0"
 
     def _forward_slices(self, parts: int, input_ids, attention_mask, pixel_values, image_attention_mask, image_states,
-                        logits_rows=None, **kw):
+                        logits_rows=None, seq_lens=None, **kw):
         dev = self.w.device
         B, S = input_ids.shape
         cut = [B * i // parts for i in range(parts + 1)]
@@ -183,13 +220,13 @@ class IdeficsEngine:
             info = torch.cat([torch.searchsorted(r, bounds), (r[1:] < r[:-1]).any().reshape(1).to(bounds.dtype)]).tolist()
             if info[-1] or r.numel() == 0:                            # not ascending (or nothing selected): one plain pass
                 return self._forward_one(input_ids, attention_mask, pixel_values, image_attention_mask, image_states,
-                                         logits_rows=logits_rows, **kw)
+                                         logits_rows=logits_rows, seq_lens=seq_lens, **kw)
             rows_of = [(r[info[i]:info[i + 1]] - cut[i] * S).contiguous() for i in range(parts)]
 
         def run(i):
             sl = lambda t: None if t is None else t[cut[i]:cut[i + 1]]
             return self._forward_one(sl(input_ids), sl(attention_mask), sl(pixel_values), sl(image_attention_mask), sl(image_states),
-                                     logits_rows=rows_of[i], **kw)
+                                     logits_rows=rows_of[i], seq_lens=seq_lens, rows=(cut[i], cut[i + 1]), **kw)
         empty = [i for i in range(parts) if logits_rows is not None and rows_of[i].numel() == 0]
         return torch.cat(run_slices(self._side_streams, dev, parts, run, skip=empty), 0)
 
@@ -256,19 +293,29 @@ class IdeficsEngine:
         """Returns logits (B, S, V) bf16 (a view with a padded row stride).
         icv: (1, n_hooked, H) fp32 — already alpha-scaled when ``alpha`` is None (the reference contract,
         ref:icv_src/icv_module.py:89-92); with ``alpha`` (1, n_hooked) fp32 the scaling is folded into the kernel.
-        hook_layers: decoder-layer ids whose OUTPUT is edited (ref:config/lmm/idefics-9B.yaml:7)."""
+        hook_layers: decoder-layer ids whose OUTPUT is edited (ref:config/lmm/idefics-9B.yaml:7).
+        Padding positions (attention_mask == 0): their logits are unspecified - no caller may read them.  On the native
+        runner they are zeros where the lengths of a right-padded batch were read for ``pack_rows`` (more than 512 rows, no KV
+        cache), whether or not the language stack then ran on packed rows (so sliced and whole forwards agree); the Python layer
+        loop zeroes them where the runner would pack (so the two paths agree there) and computes the padding tokens otherwise."""
         parts = self.batch_streams
         B, S = input_ids.shape
+        seq_lens = None
+        if attention_mask is not None and kv_cache is None and image_attention_mask is not None and B * S > ops.PACK_MIN_ROWS:
+            # ONE device-to-host read per forward, queued before the batch is cut in slices: the rows' lengths and whether every mask
+            # row is a prefix of ones (right padding); the slices decide on the host from these.  Read on every path: the Python
+            # layer loop (captures) zeroes the padding positions where the runner would pack, so the two agree at every position there
+            seq_lens = RowLengths(attention_mask)
         if (parts and parts > 1 and B >= 2 * parts and B * S >= parts * 2048 and capture is None and kv_cache is None
                 and save_hook_inputs is None and image_attention_mask is not None):
             return self._forward_slices(parts, input_ids, attention_mask, pixel_values, image_attention_mask, image_states,
-                                        logits_rows=logits_rows, icv=icv, hook_layers=hook_layers, alpha=alpha)
+                                        logits_rows=logits_rows, seq_lens=seq_lens, icv=icv, hook_layers=hook_layers, alpha=alpha)
         return self._forward_one(input_ids, attention_mask, pixel_values, image_attention_mask, image_states, icv=icv,
                                  hook_layers=hook_layers, alpha=alpha, capture=capture, kv_cache=kv_cache,
-                                 save_hook_inputs=save_hook_inputs, logits_rows=logits_rows)
+                                 save_hook_inputs=save_hook_inputs, logits_rows=logits_rows, seq_lens=seq_lens)
 
     def _forward_one(self, input_ids, attention_mask=None, pixel_values=None, image_attention_mask=None, image_states=None, icv=None,
-                     hook_layers=None, alpha=None, capture=None, kv_cache=None, save_hook_inputs=None, logits_rows=None):
+                     hook_layers=None, alpha=None, capture=None, kv_cache=None, save_hook_inputs=None, logits_rows=None, seq_lens=None, rows=None):
         a, w = self.arch, self.w
         dev = w.device
         B, S = input_ids.shape
@@ -289,13 +336,27 @@ class IdeficsEngine:
 
         past = kv_cache.len if kv_cache is not None else 0
         assert past + S == Sk, "attention_mask must span past + new tokens"
+        lo, hi = rows if rows is not None else (0, B)                    # this slice's rows of the forward's batch
+        lens = seq_lens.lens(lo, hi) if seq_lens is not None and kv_cache is None else None      # None: not right-padded / not read
         if self.use_runner and self.fuse_hook_norm and capture is None and save_hook_inputs is None and not ops.profiling():
             if self._runner is None:
                 from .runner import TextRunner
                 self._runner = TextRunner(w)
+            cu, cu_dev, pack = None, None, False
+            if lens is not None:
+                I = a.intermediate_size
+                cu_dev = seq_lens.cu_dev(lo, hi)
+                # the stack's projections: QKV, o and the cross-attention q, gate|up, down
+                cu = ops.pack_rows_plan(lens, S, [(3 * H, H), (H, H), (2 * I, H), (H, I)]) if self.pack_rows else None
+                pack = cu is not None
+                if not pack:                     # gate closed: padded rows, but zeros at the padding positions as a packed pass leaves them
+                    cu = [0]
+                    for n in lens:
+                        cu.append(cu[-1] + int(n))
             return self._runner.forward(input_ids.contiguous(), key_valid, pos, image_states.contiguous(), img_mask, gate,
                                         icv=icv, alpha=alpha.reshape(-1).contiguous() if alpha is not None else None,
-                                        hook_layers=hook_layers if idx_of else None, kv_cache=kv_cache, logits_rows=logits_rows)
+                                        hook_layers=hook_layers if idx_of else None, kv_cache=kv_cache, logits_rows=logits_rows,
+                                        cu_seqlens=cu, cu_seqlens_dev=cu_dev, pack_rows=pack)
         if kv_cache is not None and kv_cache.xkv is not None:
             kv_cache.xkv = None                      # the Python loop re-projects the cross-attention K|V at every step
         h = ops.embed_gather(input_ids.contiguous(), w.embed, w.embed_extra, a.vocab_size).view(M, H)
@@ -385,4 +446,9 @@ class IdeficsEngine:
         if capture is not None:
             capture["final_norm"] = x.view(B, S, H).clone()
             capture["image_states"] = image_states
+        I = a.intermediate_size
+        if lens is not None and ops.pack_rows_plan(lens, S, [(3 * H, H), (H, H), (2 * I, H), (H, I)]) is not None:
+            # where the native runner runs this call on packed rows it leaves zeros at the padding positions: the same here, so the
+            # two paths keep agreeing at every position; where the rows stay padded this loop computes the padding tokens as ever
+            x = x.view(B, S, H).masked_fill((attention_mask == 0)[..., None], 0).view(M, H)
         return lm_logits(x, w.lm_head, B, S, logits_rows)

@@ -584,6 +584,60 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, B: int, Sq: int
     return out
 
 
+def attention_ragged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_host: torch.Tensor, cu_seqlens_dev: torch.Tensor,
+                     Sk: int, n_heads: int, n_kv_heads: int, head_dim: int, q_rs: int, kv_bs: int, kv_rs: int, scale: float, mask_mode: int,
+                     img_mask: Optional[torch.Tensor] = None, img_len: int = 0, out: Optional[torch.Tensor] = None):
+    """licv_attn_fwd_ragged: the tiled attention of `attention` on packed rows (sequence b = rows cu[b] .. cu[b+1]-1 of q and out).
+    mask_mode 1: k / v packed like q, causal per sequence (Sk, kv_bs unused); 3: k / v (B, Sk) per batch row, img_mask (total, n_img).
+    cu_seqlens (B + 1,) int32 once on the host and once on the device.  Returns (total, nh*hd) bf16; rows of `out` past total are kept."""
+    assert cu_seqlens_host.dtype == torch.int32 and not cu_seqlens_host.is_cuda and cu_seqlens_host.is_contiguous() and cu_seqlens_host.dim() == 1
+    B = cu_seqlens_host.numel() - 1
+    if out is None:
+        out = torch.empty((int(cu_seqlens_host[-1]), n_heads * head_dim), dtype=torch.bfloat16, device=q.device)
+    a = AttnArgs()
+    a.q, a.q_bs, a.q_rs = q.data_ptr(), 0, q_rs
+    a.k, a.v, a.kv_bs, a.kv_rs = k.data_ptr(), v.data_ptr(), kv_bs, kv_rs
+    a.o = out.data_ptr()
+    a.B, a.Sq, a.Sk, a.n_heads, a.n_kv_heads, a.head_dim = B, 0, Sk, n_heads, n_kv_heads, head_dim
+    a.scale, a.mask_mode, a.key_valid = float(scale), mask_mode, None
+    if img_mask is not None:
+        assert img_mask.dtype == torch.int32 and img_mask.is_contiguous()
+        a.img_mask, a.n_img, a.img_len = img_mask.data_ptr(), img_mask.shape[-1], img_len
+    else:
+        a.img_mask, a.n_img, a.img_len = None, 0, 0
+    if cu_seqlens_dev is not None:
+        assert cu_seqlens_dev.dtype == torch.int32 and cu_seqlens_dev.is_cuda and cu_seqlens_dev.is_contiguous() and cu_seqlens_dev.shape == cu_seqlens_host.shape
+    check(_lib.lib().licv_attn_fwd_ragged(C.byref(a), C.c_void_p(cu_seqlens_host.data_ptr()), _p(cu_seqlens_dev), _stream(q)))
+    return out
+
+
+PACK_ROW_TILE = 256          # rows per GEMM tile of the large-batch route: packing pays in whole tiles
+PACK_MIN_ROWS = 512          # below it the runner takes other kernels (split-K slices summed in the row kernels, no folded residual)
+
+
+def pack_rows_plan(lens, S: int, shapes, splits=None):
+    """Whether a right-padded (B, S) slice whose rows hold `lens` real tokens runs on packed rows, as a pure function: returns
+    cu_seqlens (B + 1 ints, [0] = 0) or None = run padded.  Packed only when that drops at least one 256-row GEMM tile, leaves at
+    least 512 rows, and the split-K plan of every projection shape (N, K) in `shapes` answers the same split count for the packed row
+    count as for B * S - the condition under which real rows keep their bits.  `splits(M, N, K)` defaults to the library's plan."""
+    lens = [int(n) for n in lens]
+    B = len(lens)
+    if B == 0 or any(n < 1 or n > S for n in lens):
+        return None
+    total, full = sum(lens), B * S
+    tiles = lambda m: (m + PACK_ROW_TILE - 1) // PACK_ROW_TILE
+    if total < PACK_MIN_ROWS or tiles(total) >= tiles(full):
+        return None
+    if splits is None:
+        splits = lambda M, N, K: _splitk_plan(M, N, K)[0]          # what the native runner asks for each of its projections
+    if any(splits(total, N, K) != splits(full, N, K) for (N, K) in shapes):
+        return None
+    cu = [0]
+    for n in lens:
+        cu.append(cu[-1] + n)
+    return cu
+
+
 # ------------------------------------------------------------------------------------------ gathers
 def embed_gather(ids: torch.Tensor, table: torch.Tensor, extra: Optional[torch.Tensor], vocab: int) -> torch.Tensor:
     assert ids.dtype == torch.int64 and ids.is_contiguous()

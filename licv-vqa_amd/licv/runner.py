@@ -66,6 +66,9 @@ class TextRunner:
         lib.licv_idefics_text_forward.restype = C.c_int
         lib.licv_workspace_size.restype = C.c_int64
         self._fn = lib.licv_idefics_text_forward
+        lib.licv_idefics_text_forward_packed.argtypes = [C.POINTER(_Weights), C.POINTER(_Call), P, P, C.c_int, P, I64, P]
+        lib.licv_idefics_text_forward_packed.restype = C.c_int
+        self._fn_packed = lib.licv_idefics_text_forward_packed
         self._ws = {}
 
     def _workspace(self, M: int, rows: int, dev, xkv_rows: int = 0):
@@ -84,9 +87,13 @@ class TextRunner:
         return buf
 
     def forward(self, input_ids, key_valid, position_ids, image_states, img_mask, gate, icv=None, alpha=None,
-                hook_layers: Optional[Sequence[int]] = None, kv_cache=None, logits_rows=None):
+                hook_layers: Optional[Sequence[int]] = None, kv_cache=None, logits_rows=None, cu_seqlens: Optional[Sequence[int]] = None,
+                cu_seqlens_dev: Optional[torch.Tensor] = None, pack_rows: bool = True):
         """All tensors on the device, contiguous, in the dtypes of IdeficsEngine.forward's locals.  Returns the logits exactly as
-        that method does: (B, S, V) view (or (n_rows, V) with logits_rows)."""
+        that method does: (B, S, V) view (or (n_rows, V) with logits_rows).  cu_seqlens (B + 1 ints, the running sum of the rows'
+        lengths, and cu_seqlens_dev, the same as int32 on the device): the batch is right-padded (licv_idefics_text_forward_packed; no KV cache) and, with pack_rows (the gate of
+        ops.pack_rows_plan is open), the stack runs on its real rows only; inputs and logits keep their (B, S) layout, and logits at
+        padding positions are zeros with pack_rows and without."""
         a, w = self.arch, self.w
         dev = w.device
         B, S = input_ids.shape
@@ -137,7 +144,18 @@ class TextRunner:
         c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
         logits = torch.empty((rows, ldc), **bf)
         c.logits, c.ld_logits = logits.data_ptr(), ldc
-        check(self._fn(C.byref(self._W), C.byref(c), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if cu_seqlens is not None:
+            assert kv_cache is None and len(cu_seqlens) == B + 1
+            cu_host = torch.tensor(list(cu_seqlens), dtype=torch.int32)
+            cu_dev = cu_seqlens_dev if cu_seqlens_dev is not None else cu_host.to(dev)
+            assert cu_dev.dtype == torch.int32 and cu_dev.is_cuda and cu_dev.is_contiguous() and cu_dev.numel() == B + 1
+            keep.append(cu_dev)
+            scratch = new(int(cu_host[-1]) * (20 + 4 * int(img_mask.shape[-1])) + 16, dtype=torch.uint8, device=dev) if pack_rows else None
+            check(self._fn_packed(C.byref(self._W), C.byref(c), C.c_void_p(cu_host.data_ptr()), C.c_void_p(cu_dev.data_ptr()), 1 if pack_rows else 0,
+                                  C.c_void_p(_ptr(scratch)), 0 if scratch is None else scratch.numel(), stream))
+        else:
+            check(self._fn(C.byref(self._W), C.byref(c), stream))
         if kv_cache is not None and kv_cache.appending:
             kv_cache.len += S
         out = logits if ldc == V else logits[:, :V]
